@@ -10,7 +10,10 @@ Workload (one bench "step" = one batch of B prompts per GPU denoised end to end)
 Multi-GPU: one process per GPU (torchrun), prompts sharded data-parallel (weak scaling, B per GPU), masks
 generated on rank 0 and broadcast once over RCCL; no per-step communication.
 
-Prints ONE JSON line (rank 0). See DESIGN.md §Measurement for the roofline and baseline definitions.
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times --steps steps and prints the line (metric,
+value, ms_per_step, ...); --dump-outputs DIR also writes what the last timed step returned. Everything else the
+benchmark measures -- the conv-family roofline, the end-to-end (text encoder + VAE) steps, the CPU baseline -- runs
+only with --full. See DESIGN.md §Measurement for the roofline and baseline definitions.
 """
 from __future__ import annotations
 
@@ -53,17 +56,25 @@ def parse():
     p.add_argument("--topk-mask", choices=["down", "pass"], default="down",
                    help="down: the top-k mask is applied by the down projection as it reads the GEGLU product "
                         "(sdmoe_linear_keep); pass: a separate masking pass over the product (A/B reference)")
+    p.add_argument("--full", action="store_true",
+                   help="besides the metric run: the conv-family roofline (HIP events around sampled conv launches of "
+                        "the timed steps), the end-to-end steps (--e2e-steps) and the CPU baseline; without it those "
+                        "three are off and their keys of the result line are null")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step returned (this rank's images: the "
+                        "denoised latents, or RGB with --decode) to DIR/<name>.npy as float32; the inputs are seeded, "
+                        "so two builds run with the same arguments can be compared output for output")
     p.add_argument("--decode", action="store_true",
                    help="also run the CLIP text encoder and the VAE decoder inside the timed step (end-to-end "
                         "images; the metric excludes them, SURVEY §8d)")
     p.add_argument("--e2e-steps", type=int, default=1,
-                   help="after the timed metric run, time this many end-to-end steps (text encoder + denoise + VAE "
-                        "decode to RGB) and report them as 'end_to_end' (0: skip)")
-    p.add_argument("--no-roofline", action="store_true")
+                   help="--full: after the timed metric run, time this many end-to-end steps (text encoder + denoise "
+                        "+ VAE decode to RGB) and report them as 'end_to_end' (0: skip)")
+    p.add_argument("--no-roofline", action="store_true", help="--full without the roofline")
     p.add_argument("--roofline-sample", type=int, default=25,
-                   help="time the conv launches of every N-th U-Net evaluation (1 = every launch; event markers idle "
-                        "the GPU ~5.7 us each)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+                   help="--full: time the conv launches of every N-th U-Net evaluation (1 = every launch; event markers "
+                        "idle the GPU ~5.7 us each)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--cpu-evals", type=int, default=2, help="CPU oracle U-Net evaluations to time")
     p.add_argument("--cpu-full-image", action="store_true",
                    help="cpu_baseline: time one whole image (all inference steps of the oracle's DDIM+CFG loop, "
@@ -73,7 +84,10 @@ def parse():
                    help="PMC summary json from tools/pmc_traffic.py (HBM bytes per conv launch); default "
                         "profiles/pmc_conv_traffic.json (8 prompts/GPU) or profiles/pmc_conv_traffic_b<B>.json; used "
                         "only when its recorded model / prompts per GPU / mask are this run's")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:  # a plain run measures the metric only
+        args.no_roofline, args.no_cpu_baseline, args.e2e_steps = True, True, 0
+    return args
 
 
 def launch_ranks(n, argv):
@@ -326,6 +340,24 @@ def cpu_baseline(args):
                       f"{dt:.2f} s each, x{args.inference_steps} steps per image"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, images, rank, world):
+    """--dump-outputs: the images one_step returned (a list of per-prompt tensors), stacked, as float32 in
+    DIR/images.npy (DIR/images_rank<r>.npy per rank when world > 1). An output above the size limit is written as
+    a fixed, seeded sample of its elements (DIR/images_sample_index.npy holds their flat indices)."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    arr = torch.stack([x.detach().float() for x in images]).cpu().numpy().astype(np.float32)
+    if arr.nbytes > DUMP_LIMIT_BYTES // 2:
+        n = DUMP_LIMIT_BYTES // 2 // 12  # float32 value + int64 index per element
+        idx = np.sort(np.random.default_rng(0).choice(arr.size, size=n, replace=False))
+        np.save(os.path.join(dirname, f"images_sample_index{sfx}.npy"), idx)
+        arr = arr.reshape(-1)[idx]
+    np.save(os.path.join(dirname, f"images{sfx}.npy"), arr)
+
+
 def metric_label(args):
     """BASELINE.json's metric string for the default run (SD-1.4, 50 DDIM steps); other runs say what they ran."""
     sched = f"{args.inference_steps}-step {args.scheduler.upper()}"
@@ -412,6 +444,8 @@ def main():
         dist.barrier()
     elapsed = D.max_over_ranks(t1 - t0, dev)
     finite = all(bool(torch.isfinite(x).all()) for x in imgs)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, imgs, rank, world)
     images = world * args.batch * args.steps
     value = images / elapsed
 

@@ -23,11 +23,11 @@ step() {  # step NAME SECONDS CMD...: run, keep the log, stop everything on fail
   if [ $rc -ne 0 ]; then echo "FAILED $name rc=$rc"; tail -30 $O/$name.log; exit $rc; fi
   grep -a '^{' $O/$name.log | tail -1 | cut -c1-600
 }
-BA="--no-cpu-baseline --e2e-steps 0"
+BA="--full --no-cpu-baseline --e2e-steps 0"  # the roofline only (the trace / pmc steps below run plain)
 for s in $STEPS; do
   cd $R
   case $s in
-    bench) step bench 600 python bench.py --steps 10 --warmup 2 ;;
+    bench) step bench 600 python bench.py --full --steps 10 --warmup 2 ;;
     union) step bench_union 600 python bench.py --mask union --steps 5 --warmup 1 $BA ;;
     sdxl) step bench_sdxl 600 python bench.py --model sdxl --steps 2 --warmup 1 $BA ;;
     none) step bench_none 600 python bench.py --mask none --steps 5 --warmup 1 $BA ;;
