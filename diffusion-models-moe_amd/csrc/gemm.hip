@@ -16,7 +16,9 @@
 // deterministic ordered reduce kernel that also runs the epilogue.
 // Epilogue (fused): + bias[n] + coladd[image][n] (time embedding) -> activation -> + residual[m][n],
 // staged through LDS so stores are 16 B per lane.
+#include <array>
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "../../include/sdmoe.h"
@@ -35,8 +37,6 @@ int g_mfast = 1;   // knob 14: split-K conv grids ordered M-tile fastest (1) or 
 // there is no residual (LN-folded projections 4-12 %, plain K = 320 linears ~3 % faster; with a residual its 16-B
 // residual loads measured 3-7 % slower than the staged copy-out), 2 = always, 0 = never
 int g_epi_direct = 1;
-int g_cus = 256;  // compute units of the device (device_cus(): hipDeviceAttributeMultiprocessorCount, queried once)
-bool g_cus_init = false;
 int g_diag = 0;  // knob 6, diagnostics only (results garbage): bit 0 = no K-loop operand loads, bit 1 = no MFMAs,
                  // bit 4 = no A-operand pieces, bit 5 = no B-operand pieces,
                  // bit 2 = no epilogue (nothing stored), bit 3 = epilogue without its global stores
@@ -97,7 +97,6 @@ struct GemmParams {
   const float* gn_scale; const float* gn_shift; int gn_silu;
 };
 
-SDMOE_DEV int swz(int row) { return (row >> 1) & 7; }
 SDMOE_DEV bool g_res16_dev(const GemmParams& p) { return p.res16 != 0; }
 
 constexpr unsigned OOB = 0x80000000u;  // > every num_records used here (tensors < 2 GiB)
@@ -175,18 +174,21 @@ constexpr bool mode_wmask(int mode) { return mode == MODE_WMASK || mode == MODE_
 
 // LDS bytes one ring stage holds besides the A/B tiles: the mask bytes of the tile's rows for one 64-deep K-step
 // (A keep: BM rows x 8 bytes; W mask: BN rows x 8 bytes; each in whole 1-KiB LDS-DMA pieces)
+constexpr int keep_a_bytes(int bm, int mode) { return mode_akeep(mode) ? ((bm * 8 + 1023) / 1024) * 1024 : 0; }
+constexpr int keep_w_bytes(int bn, int mode) { return mode_wmask(mode) ? ((bn * 8 + 1023) / 1024) * 1024 : 0; }
+constexpr int keep_stage_bytes(int bm, int bn, int mode) { return keep_a_bytes(bm, mode) + keep_w_bytes(bn, mode); }
+// (the kernel's spellings of the same constants; the host's launch planning calls the functions above)
 template <int BM, int MODE>
-constexpr int keep_a_bytes() { return mode_akeep(MODE) ? ((BM * 8 + 1023) / 1024) * 1024 : 0; }
-template <int BN, int MODE>
-constexpr int keep_w_bytes() { return mode_wmask(MODE) ? ((BN * 8 + 1023) / 1024) * 1024 : 0; }
+constexpr int keep_a_bytes() { return keep_a_bytes(BM, MODE); }
 template <int BM, int BN, int MODE>
-constexpr int keep_stage_bytes() { return keep_a_bytes<BM, MODE>() + keep_w_bytes<BN, MODE>(); }
+constexpr int keep_stage_bytes() { return keep_stage_bytes(BM, BN, MODE); }
 // MODE_KEEP: a keep byte (8 neurons) -> 4 x 32-bit masks of the 8 fp16 halves, one ds_read_b128 per A fragment
 // (round 5: two dependent ds_read_b64 from a 16-entry nibble table: keep-masked down projections 1.5-3 % slower);
 // the W-masked modes keep the nibble table (the byte table there cost the 128x160 KEEPW tile its second workgroup
 // per CU: 173 -> 268 VGPRs)
+constexpr int keep_lut_bytes(int mode) { return mode == MODE_KEEP ? 256 * 16 : 16 * 8; }
 template <int MODE>
-constexpr int keep_lut_bytes() { return MODE == MODE_KEEP ? 256 * 16 : 16 * 8; }
+constexpr int keep_lut_bytes() { return keep_lut_bytes(MODE); }
 
 // Routed-GEGLU expert scores over one staged pass of a wave's tile: the activated gates (fp16) of RG rows x NH
 // neurons, experts = contiguous S-neuron slices (neurons pre-permuted expert-major). score = fp32 sum in neuron order,
@@ -1379,11 +1381,15 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmParams p) {
 }
 
 // ---- launch planning (host only) ----------------------------------------------------------------------------
-// A launch = a tile instantiation + a split-K factor. The split (with the 64-deep K walk every tile shares) is the
-// only thing that decides each output's fp32 summation order -- tile shape and wave arrangement do not -- so it is
-// computed by ONE function (plan_split) from the chosen tile, and the masked modes (MODE_KEEP / WMASK / KEEPW) take
-// the plain GEMM's plan for their shape (dispatch below): a keep- or Wanda-masked product is bit-identical to masking
-// the operand first and running sdmoe_linear by construction, not by a restated copy of the plain rules.
+// A launch is a Plan: everything the host decides about it. Three planners make one from the GemmParams shape fields,
+// the knobs, device_cus() and the workspace's presence and size, dereferencing no pointer and launching nothing:
+// plan_launch (dense and masked linears, shifted-tile convs), plan_geglu, plan_halo. launch() runs a plan;
+// sdmoe_gemm_plan / sdmoe_conv_plan report one.
+// The split (with the K walk every tile of a family shares) is the only thing that decides each output's fp32
+// summation order -- tile shape and wave arrangement do not -- so the dense split is computed by ONE function
+// (plan_split) from the chosen tile, and the masked modes (MODE_KEEP / WMASK / KEEPW) take the plain GEMM's plan for
+// their shape: a keep- or Wanda-masked product is bit-identical to masking the operand first and running sdmoe_linear
+// by construction, not by a restated copy of the plain rules.
 enum TileId { T128x160, T64x160, T256x320, T256x160_42, T256x320_42, T128x320, T128x160_42, T64x320, T128x32, T128x64,
               T128x128, T64x128, NTILE };
 struct TileShape { int bm, bn, wmw, wnw; };
@@ -1391,26 +1397,49 @@ constexpr TileShape kTile[NTILE] = {{128, 160, 2, 2}, {64, 160, 2, 2}, {256, 320
                                     {256, 320, 4, 2}, {128, 320, 2, 4}, {128, 160, 4, 2}, {64, 320, 2, 4},
                                     {128, 32, 2, 2},  {128, 64, 2, 2},  {128, 128, 2, 2}, {64, 128, 2, 2}};
 struct Plan {
-  int tile;
-  int ks_want;      // split-K wish of the tile rule (0 = the policy in plan_split)
-  int stages_want;  // LDS ring depth wish (0 = launch_tile's policy)
+  int mode;     // the kernel's MODE; mode_halo(mode) = the halo-conv family, else the shifted / plain tile family
+  int tile;     // TileId (halo: BM x 320 on 2 x 4 waves, T128x320 or T256x320)
+  int bk, stages;  // the LDS ring: K depth of one stage, 64 (tiles) or 32 (halo), and its slots
+  int ksplit;   // split-K factor (> 1: fp32 slabs in the workspace + splitk_reduce_kernel)
+  int kchunk;   // K units per split: 64-deep K-steps (tiles) or 32-channel slices of the main input (halo)
+  int kchunk2;  // halo: folded-shortcut K-steps per split
+  int mfast;    // tile order M-fastest
 };
+// a tile rule's choice: the tile, its split-K wish (0 = plan_split's policy), its ring depth wish (0 = tile_plan's)
+struct TileRule { int tile, ks_want, stages_want; };
 
-// compute units of the current device, queried once (both split policies size their grids by it; 256 on MI355X, and
-// the fallback when no device answers, e.g. sdmoe_gemm_plan on a CPU host). Splits -- hence the fp32 summation order
-// of split-K outputs -- are per-device-SKU by design.
+// the gemm_kernel instantiations the library is built with: launch() reaches exactly these
+constexpr bool mode_geglu(int mode) { return mode == MODE_GEGLU || mode == MODE_GEGLU_LN || mode == MODE_GEGLU_GT; }
+constexpr bool built(int mode, int tile) {
+  if (mode_halo(mode)) return (tile == T128x320 && mode != MODE_CONVHUP64) || (tile == T256x320 && mode != MODE_CONVHUP16);
+  if (mode_geglu(mode))  // BN in {160, 320} only (wave tile width 80 = 40 neurons = whole experts)
+    return tile == T128x160 || tile == T64x160 || tile == T256x320 || tile == T256x160_42 || tile == T256x320_42 ||
+           (tile == T128x160_42 && mode != MODE_GEGLU_GT);  // (no room for the GELU table behind that tile's staging)
+  if (tile == T128x160_42 || tile == T64x320) return mode == MODE_GEMM || mode == MODE_CONV || mode == MODE_GEMM_LN;
+  if (tile == T128x32) return mode == MODE_CONV;
+  return true;
+}
+// whether a 3-slot ring of 64-deep stages (+ keep bytes, mask table, LayerNorm row statistics) fits the 160 KiB of LDS
+constexpr bool fits3(int bm, int bn, int mode) {
+  return 3 * ((bm + bn) * 64 * 2 + 1024 + keep_stage_bytes(bm, bn, mode)) +
+             (keep_stage_bytes(bm, bn, mode) ? keep_lut_bytes(mode) : 0) +
+             ((mode == MODE_GEMM_LN || mode == MODE_GEGLU_LN) ? bm * 8 + bn * 8 : 0) <= 160 * 1024;
+}
+
+// compute units of the current device (both split policies size their grids by it; 256 on MI355X), latched after the
+// first query that succeeds; 256 while no device answers, e.g. sdmoe_gemm_plan on a CPU host. Splits -- hence the fp32
+// summation order of split-K outputs -- are per-device-SKU by design.
 int device_cus() {
-  if (g_cus_init) return g_cus;
+  static int cus = 0;
   int dev = 0, n = 0;
-  if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) ==
-      hipSuccess && n > 0)
-    g_cus = n;
-  g_cus_init = true;
-  return g_cus;
+  if (!cus && hipGetDevice(&dev) == hipSuccess &&
+      hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
+    cus = n;
+  return cus ? cus : 256;
 }
 
 // split-K factor of a launch on tile t (mode: the tile rule's MODE; ws: whether a slab workspace was handed in)
-int plan_split(const TileShape& t, int mode, const GemmParams& p, const float* ws, long ws_floats, int ks_want) {
+int plan_split(const TileShape& t, int mode, const GemmParams& p, bool ws, long ws_floats, int ks_want) {
   const int ntiles = ((p.M + t.bm - 1) / t.bm) * ((p.N + t.bn - 1) / t.bn);
   const int nk = p.K / 64;
   const int cus = device_cus();
@@ -1419,7 +1448,6 @@ int plan_split(const TileShape& t, int mode, const GemmParams& p, const float* w
   if (ws && (g_ksplit > 0 || ks_want > 0)) {
     ksplit = g_ksplit > 0 ? g_ksplit : ks_want;
     if (ksplit > nk) ksplit = nk;
-    while (ksplit > 1 && (long)ksplit * p.M * p.N > ws_floats) --ksplit;
   } else if (ws && (mode == MODE_CONV || mode == MODE_CONV_UP) && ntiles <= 16 && nk >= 64) {
     // latency regime (one prompt per call, base_receiver.py:73: 8x8 / 16x16 / 32x32 convs at batch 2): up to two
     // workgroups per CU, >= 11 K-steps per split, <= 64 MB of fp32 slabs -- B = 1 sweep (profiles/r05_b1_split_sweep.txt):
@@ -1429,13 +1457,12 @@ int plan_split(const TileShape& t, int mode, const GemmParams& p, const float* w
     if (ksplit > 24) ksplit = 24;
     if (ksplit > nk / 11) ksplit = nk / 11;
     while (ksplit > 1 && (long)ksplit * p.M * p.N * 4 > (64L << 20)) --ksplit;
-    while (ksplit > 1 && (long)ksplit * p.M * p.N > ws_floats) --ksplit;
   } else if (ws && ntiles < 3 * cus / 4 && nk >= 16) {
     ksplit = (cus + ntiles - 1) / ntiles;
     if (ksplit > 8) ksplit = 8;
     if (ksplit > nk / 4) ksplit = nk / 4;
-    while (ksplit > 1 && (long)ksplit * p.M * p.N > ws_floats) --ksplit;
   }
+  while (ksplit > 1 && (long)ksplit * p.M * p.N > ws_floats) --ksplit;  // the slabs fit the workspace
   if (ksplit < 1) ksplit = 1;
   // no empty trailing split: ceil(nk / ksplit) K-steps per split, as many splits as that takes (e.g. nk = 180 at 16
   // wanted: 12 per split -> 15 splits, not a 16th that writes a zero slab the reduce then reads)
@@ -1443,50 +1470,25 @@ int plan_split(const TileShape& t, int mode, const GemmParams& p, const float* w
   return (nk + kchunk - 1) / kchunk;
 }
 
-template <int BM, int BN, int WMW, int WNW, int MODE>
-int launch_tile(GemmParams p, float* ws, hipStream_t s, int ksplit, int stages_want = 0) {
-  const int ntiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
+// the plan of a tile-family launch from its tile, split and ring-depth wish
+Plan tile_plan(int mode, int tile, const GemmParams& p, int ksplit, int stages_want) {
+  const TileShape& t = kTile[tile];
+  const int ntiles = ((p.M + t.bm - 1) / t.bm) * ((p.N + t.bn - 1) / t.bn);
   const int nk = p.K / 64;
-  if (p.w_bstride && p.rows_per_batch % BM) return SDMOE_EUNSUP;  // a tile would straddle two images' weights
-  if (ksplit > 1 && !ws) return SDMOE_EARG;
-  p.ksplit = ksplit > 1 ? ksplit : 1;
-  constexpr int NTH = 64 * WMW * WNW;
-  p.kchunk = (nk + p.ksplit - 1) / p.ksplit;
-  p.part = p.ksplit > 1 ? ws : nullptr;
+  Plan pl{};
+  pl.mode = mode; pl.tile = tile; pl.bk = 64; pl.ksplit = ksplit;
+  pl.kchunk = (nk + ksplit - 1) / ksplit;
   // M-fastest order for split-K convs only: their weight slices (up to 29 MB at the 16x16 level) were re-fetched by
   // every XCD (PMC FETCH_SIZE of the split-K conv launches 140 -> 46 MB, time neutral); the M = 1024 split-K linears
   // measured 2 us slower with it
-  p.mfast = (p.ksplit > 1 && g_mfast && (MODE == MODE_CONV || MODE == MODE_CONV_UP)) ? 1 : 0;
-  p.diag = g_diag;
-  p.epi_direct = g_epi_direct == 2 || (g_epi_direct == 1 && p.R == nullptr);  // host-side: a device test of R spilled
-  p.res16 = g_res16;
-  const dim3 grid(ntiles * p.ksplit);
-  {
-    // 64-deep K-steps (a 32-deep 4/5-stage ring measured slower on every shape; the kernel is generic in BK).
-    // 4-wave tiles: 2-stage ring (2 workgroups/CU) when the grid has >= ~300 workgroups, else 3-stage; 8-wave
-    // tiles: 3-stage where it fits in LDS -- measured crossovers on MI355X.
-    const int stages = g_stages ? g_stages
-                                : (stages_want ? stages_want : ((WMW * WNW == 4 && ntiles * p.ksplit >= 300) ? 2 : 3));
-    constexpr bool FITS3 = 3 * ((BM + BN) * 64 * 2 + 1024 + keep_stage_bytes<BM, BN, MODE>()) +
-                               (keep_stage_bytes<BM, BN, MODE>() ? keep_lut_bytes<MODE>() : 0) +
-                               ((MODE == MODE_GEMM_LN || MODE == MODE_GEGLU_LN) ? BM * 8 + BN * 8 : 0) <= 160 * 1024;
-    if constexpr (FITS3) {
-      if (stages == 2) gemm_kernel<BM, BN, WMW, WNW, MODE, 2, 64><<<grid, NTH, 0, s>>>(p);
-      else gemm_kernel<BM, BN, WMW, WNW, MODE, 3, 64><<<grid, NTH, 0, s>>>(p);
-    } else {
-      (void)stages;
-      gemm_kernel<BM, BN, WMW, WNW, MODE, 2, 64><<<grid, NTH, 0, s>>>(p);
-    }
-  }
-  SDMOE_CHECK_LAUNCH();
-  if (p.ksplit > 1) {
-    long nchunk = (long)p.M * (p.N / 8);
-    int g = (int)((nchunk + 255) / 256);
-    if (g > 2048) g = 2048;
-    splitk_reduce_kernel<<<g, 256, 0, s>>>(p);
-    SDMOE_CHECK_LAUNCH();
-  }
-  return SDMOE_OK;
+  pl.mfast = (pl.ksplit > 1 && g_mfast && (mode == MODE_CONV || mode == MODE_CONV_UP)) ? 1 : 0;
+  // 64-deep K-steps (a 32-deep 4/5-stage ring measured slower on every shape; the kernel is generic in BK).
+  // 4-wave tiles: 2-stage ring (2 workgroups/CU) when the grid has >= ~300 workgroups, else 3-stage; 8-wave
+  // tiles: 3-stage where it fits in LDS -- measured crossovers on MI355X.
+  const int stages = g_stages ? g_stages
+                              : (stages_want ? stages_want : ((t.wmw * t.wnw == 4 && ntiles * pl.ksplit >= 300) ? 2 : 3));
+  pl.stages = (stages == 2 || !fits3(t.bm, t.bn, mode)) ? 2 : 3;
+  return pl;
 }
 
 // knob 16: halo-tiled stride-1 3x3 convs: 1 (default) = where they measured faster than the shifted-tile kernel:
@@ -1496,18 +1498,15 @@ int launch_tile(GemmParams p, float* ws, hipStream_t s, int ksplit, int stages_w
 // every 32-wide output on 256-row tiles (135.1 vs 118.0 us at 640 -> 640); 0 = off
 int g_halo = 1;
 
-// halo conv launch: BM x 320 tiles (8 waves 2 x 4, BK 32, 3-stage B ring), K split over whole 32-channel slices when
-// the tile grid is under ~one wave of CUs
-template <int BM, int MODE>
-int launch_halo(GemmParams p, float* ws, long ws_floats, hipStream_t s) {
+// the plan of a halo conv on tile (BM x 320, 8 waves 2 x 4, BK 32, 4-slot B ring): K split over whole 32-channel slices
+// when the tile grid is under ~one wave of CUs
+Plan halo_plan(int tile, int mode, const GemmParams& p, bool ws, long ws_floats) {
   const int cus = device_cus();
-  constexpr int HW_ = halo_w(MODE);
-  const int ntiles = (p.M / BM) * (p.N / 320);
+  const int ntiles = (p.M / kTile[tile].bm) * (p.N / 320);
   const int nsl = p.Cin / 32;
   int ksplit = 1;
   if (ws && g_ksplit > 0) {  // forced (knob 9, sweeps): at most one 32-channel slice per split
     ksplit = g_ksplit < nsl ? g_ksplit : nsl;
-    while (ksplit > 1 && (long)ksplit * p.M * p.N > ws_floats) --ksplit;
   } else if (ws && ntiles <= 32) {
     // latency regime (batch 2: whole 16x16 images, the 8 -> 16 upsample, 64x64 at 32 tiles): up to two workgroups
     // per CU, >= 2 slices per split, <= 96 MB of fp32 slabs -- B = 1 sweep: 16x16 1280 -> 1280 56.1 -> 40.9 us
@@ -1519,81 +1518,69 @@ int launch_halo(GemmParams p, float* ws, long ws_floats, hipStream_t s) {
     // round (8 -> 16 upsample at one prompt: 43.2 vs 30.9 us with 16 splits, profiles/r05_b1_conv_split_sweep.txt)
     if (ntiles * ksplit > cus && ntiles <= cus) ksplit = (cus / ntiles) * ((ksplit * ntiles) / cus);
     while (ksplit > 1 && (long)ksplit * p.M * p.N * 4 > (96L << 20)) --ksplit;
-    while (ksplit > 1 && (long)ksplit * p.M * p.N > ws_floats) --ksplit;
-    if (ksplit < 1) ksplit = 1;
   } else if (ws && ntiles < 200) {
     ksplit = (cus + ntiles - 1) / ntiles;  // 6 / 8 splits: 172 vs 128 us at 16x16 x 1280 (r04)
     if (ksplit > 8) ksplit = 8;
     if (ksplit > nsl / 2) ksplit = nsl / 2;
-    while (ksplit > 1 && (long)ksplit * p.M * p.N > ws_floats) --ksplit;
-    if (ksplit < 1) ksplit = 1;
   }
-  const int slc = (nsl + ksplit - 1) / ksplit;   // main slices per split
-  p.ksplit = (nsl + slc - 1) / slc;
-  p.kchunk = slc;
-  p.kchunk2 = p.A2 ? ((p.K - 9 * p.Cin) / 32 + p.ksplit - 1) / p.ksplit : 0;  // shortcut steps per split
-  p.part = p.ksplit > 1 ? ws : nullptr;
-  p.mfast = p.ksplit > 1 ? g_mfast : 0;
-  p.diag = g_diag;
-  p.epi_direct = g_epi_direct == 2 || (g_epi_direct == 1 && p.R == nullptr);  // host-side: a device test of R spilled
-  p.res16 = g_res16;
-  (void)HW_;
-  gemm_kernel<BM, 320, 2, 4, MODE, 4, 32><<<dim3(ntiles * p.ksplit), 512, 0, s>>>(p);
-  SDMOE_CHECK_LAUNCH();
-  if (p.ksplit > 1) {
-    long nchunk = (long)p.M * (p.N / 8);
-    int g = (int)((nchunk + 255) / 256);
-    if (g > 2048) g = 2048;
-    splitk_reduce_kernel<<<g, 256, 0, s>>>(p);
-    SDMOE_CHECK_LAUNCH();
-  }
-  return SDMOE_OK;
+  while (ksplit > 1 && (long)ksplit * p.M * p.N > ws_floats) --ksplit;  // the slabs fit the workspace
+  if (ksplit < 1) ksplit = 1;
+  Plan pl{};
+  pl.mode = mode; pl.tile = tile; pl.bk = 32; pl.stages = 4;
+  pl.kchunk = (nsl + ksplit - 1) / ksplit;
+  pl.ksplit = (nsl + pl.kchunk - 1) / pl.kchunk;
+  pl.kchunk2 = ((p.K - 9 * p.Cin) / 32 + pl.ksplit - 1) / pl.ksplit;
+  pl.mfast = pl.ksplit > 1 ? g_mfast : 0;
+  return pl;
 }
 
-// stride-1, non-upsampling 3x3 conv (+ folded shortcut) on a halo tile: image widths 64 (256-row tiles = 4
-// output rows), 32 and 16 (128-row tiles), N a multiple of 320; otherwise -1 (the shifted-tile path)
-int try_halo(const GemmParams& p, float* ws, long ws_floats, hipStream_t s) {
-  if (!g_halo || g_tile || p.stride != 1 || p.N % 320 || p.Cin % 32 || (p.K - 9 * p.Cin) % 32) return -1;
+// stride-1 or upsampling 3x3 conv (+ folded shortcut: the K-steps past 9 * Cin) on halo tiles: output widths 64, 32
+// and 16, N a multiple of 320; false = not a halo shape (the shifted-tile path, plan_launch). gn: the conv applies a
+// GroupNorm to its staged input (sdmoe_conv3x3_gn), which only the 64-wide tiles over whole 256-row groups do, for up
+// to the kernel's GN_MAXC = 1280 channels of fp32 scale + shift in LDS
+bool plan_halo(const GemmParams& p, bool ws, long ws_floats, bool gn, Plan* pl) {
+  if (!g_halo || g_tile || p.stride != 1 || p.N % 320 || p.Cin % 32 || (p.K - 9 * p.Cin) % 32) return false;
+  if (gn && (p.upsample || p.Wd != 64 || (p.H * p.Wd) % 256 || p.Cin > 1280)) return false;
+  const auto take = [&](int tile, int mode) { *pl = halo_plan(tile, mode, p, ws, ws_floats); return true; };
   if (p.upsample) {  // output width 2 W, output rows per image 2 H
-    if (p.A2) return -1;
+    if (p.K != 9 * p.Cin) return false;
     const int ohw = 4 * p.H * p.Wd;
-    if (p.Wd == 32 && ohw % 256 == 0) return launch_halo<256, MODE_CONVHUP64>(p, ws, ws_floats, s);
-    if (p.Wd == 8 && ohw % 128 == 0) return launch_halo<128, MODE_CONVHUP16>(p, ws, ws_floats, s);  // 125.6 vs 137.0
+    if (p.Wd == 32 && ohw % 256 == 0) return take(T256x320, MODE_CONVHUP64);
+    if (p.Wd == 8 && ohw % 128 == 0) return take(T128x320, MODE_CONVHUP16);  // 125.6 vs 137.0
     // one prompt per call (<= 32 tiles of 256 output rows): 128-row tiles, 68.8 vs 72.5 us at 2 images
     if (g_halo == 1 && p.Wd == 16 && ohw % 128 == 0 && (p.M / 256) * (p.N / 320) <= 32)
-      return launch_halo<128, MODE_CONVHUP32>(p, ws, ws_floats, s);
+      return take(T128x320, MODE_CONVHUP32);
     // 16 -> 32 upsample on 256-row tiles (8 output rows, K split over slices): 360.3 vs 383.1-395.8 us
-    if (g_halo != 2 && p.Wd == 16 && ohw % 256 == 0) return launch_halo<256, MODE_CONVHUP32>(p, ws, ws_floats, s);
-    if (g_halo < 2) return -1;
-    if (p.Wd == 16 && ohw % 128 == 0) return launch_halo<128, MODE_CONVHUP32>(p, ws, ws_floats, s);  // 449 vs 383 us
-    return -1;
+    if (g_halo != 2 && p.Wd == 16 && ohw % 256 == 0) return take(T256x320, MODE_CONVHUP32);
+    if (g_halo < 2) return false;
+    if (p.Wd == 16 && ohw % 128 == 0) return take(T128x320, MODE_CONVHUP32);  // 449 vs 383 us
+    return false;
   }
   const int hw = p.H * p.Wd;
   // 64-wide outputs at one prompt (<= 32 tiles of 256 rows): 128-row tiles (two output rows), twice the workgroups
   // for the split to fill the chip with: 33.6 vs 41.0 us (320 -> 320) and 43.5 vs 51.1 (640 -> 320) at 2 images,
   // --batch 1 +0.8 % (profiles/r05_halo64_b1.txt)
   if (g_halo == 1 && p.Wd == 64 && hw % 128 == 0 && (p.M / 256) * (p.N / 320) <= 32)
-    return launch_halo<128, MODE_CONVH64>(p, ws, ws_floats, s);
-  if (p.Wd == 64 && hw % 256 == 0) return launch_halo<256, MODE_CONVH64>(p, ws, ws_floats, s);
+    return take(T128x320, MODE_CONVH64);
+  if (p.Wd == 64 && hw % 256 == 0) return take(T256x320, MODE_CONVH64);
   // one prompt per call (<= 32 tiles of 256 rows): 128-row tiles for the 16-wide and the narrow-input 32-wide convs,
   // twice the workgroups for the split -- 31.9 vs 39.9 us (16x16 1280 -> 1280), 32.3 vs 35.2 (32x32 640 -> 640), 38.9
   // vs 41.3 (960 -> 640) at 2 images; the Cin >= 1280 32-wide convs keep 256-row tiles (57.8 vs 52.0 us)
   // (profiles/r05_halo128_b1.txt)
   const bool small = (p.M / 256) * (p.N / 320) <= 32;
-  if (g_halo == 1 && small && p.Wd == 16 && hw % 128 == 0) return launch_halo<128, MODE_CONVH16>(p, ws, ws_floats, s);
-  if (g_halo == 1 && small && p.Wd == 32 && hw % 128 == 0 && p.Cin < 1280)
-    return launch_halo<128, MODE_CONVH32>(p, ws, ws_floats, s);
+  if (g_halo == 1 && small && p.Wd == 16 && hw % 128 == 0) return take(T128x320, MODE_CONVH16);
+  if (g_halo == 1 && small && p.Wd == 32 && hw % 128 == 0 && p.Cin < 1280) return take(T128x320, MODE_CONVH32);
   // 16-wide outputs: a whole 16x16 image per 256-row tile, K split over slices (1280 -> 1280: 127.6 vs 133.0 us)
-  if (g_halo != 2 && p.Wd == 16 && hw % 256 == 0) return launch_halo<256, MODE_CONVH16>(p, ws, ws_floats, s);
+  if (g_halo != 2 && p.Wd == 16 && hw % 256 == 0) return take(T256x320, MODE_CONVH16);
   // 32-wide outputs: halo tiles (8 output rows) for the wide-input convs only (up-block conv1, Cin 1920 / 1280): 292 vs
   // 307 us and 206 vs 208 at 16 images, 62 vs 66 and 52 vs 54 at 2; at Cin 640 / 960 they ran 10-14 % slower
   // (profiles/r05_halo32_geglu_diag.txt)
-  if (g_halo == 1 && p.Wd == 32 && hw % 256 == 0 && p.Cin >= 1280) return launch_halo<256, MODE_CONVH32>(p, ws, ws_floats, s);
-  if (g_halo == 3 && p.Wd == 32 && hw % 256 == 0) return launch_halo<256, MODE_CONVH32>(p, ws, ws_floats, s);
-  if (g_halo < 2) return -1;
-  if (p.Wd == 32 && hw % 128 == 0) return launch_halo<128, MODE_CONVH32>(p, ws, ws_floats, s);
-  if (p.Wd == 16 && hw % 128 == 0) return launch_halo<128, MODE_CONVH16>(p, ws, ws_floats, s);
-  return -1;
+  if (g_halo == 1 && p.Wd == 32 && hw % 256 == 0 && p.Cin >= 1280) return take(T256x320, MODE_CONVH32);
+  if (g_halo == 3 && p.Wd == 32 && hw % 256 == 0) return take(T256x320, MODE_CONVH32);
+  if (g_halo < 2) return false;
+  if (p.Wd == 32 && hw % 128 == 0) return take(T128x320, MODE_CONVH32);
+  if (p.Wd == 16 && hw % 128 == 0) return take(T128x320, MODE_CONVH16);
+  return false;
 }
 
 // knob 20: 1 (default) = the table-GELU GEGLU on the 256x320 2x4-wave tiles like the ReLU one (no scratch since the
@@ -1603,37 +1590,32 @@ int g_gt320 = 1;
 int g_narrow = 1;  // knob 21: 1 (default) = N <= 32 conv outputs (conv_out's 8 padded channels) on 128x32 tiles
                    // (31.9 vs 34.8-35.1 us at 64x64 x 320 -> 8, same box), 0 = 128x64
 
-// routed-GEGLU linear: BN in {160, 320} tiles only (wave tile width 80 = 40 neurons = whole experts), no split-K
-template <int MODE>
-int dispatch_geglu(const GemmParams& p, hipStream_t s) {
+// routed-GEGLU linear (MODE_GEGLU / GEGLU_LN / GEGLU_GT): BN in {160, 320} tiles only, no split-K
+Plan plan_geglu(int mode, const GemmParams& p) {
   const int nt320 = ((p.M + 255) / 256) * (p.N / 320);
   const int nt160_128 = ((p.M + 127) / 128) * (p.N / 160);
-  if (g_tile == 1) return launch_tile<128, 160, 2, 2, MODE>(p, nullptr, s, 1);
-  if (g_tile == 4) return launch_tile<256, 160, 4, 2, MODE>(p, nullptr, s, 1);
-  if constexpr (MODE != MODE_GEGLU_GT)  // (no room for the GELU table behind that tile's staging)
-    if (g_tile == 7) return launch_tile<128, 160, 4, 2, MODE>(p, nullptr, s, 1);  // sweep: two workgroups per CU
-  if (MODE == MODE_GEGLU_GT && g_tile == 0 && !g_gt320 && p.N % 320 == 0 && nt320 >= 240)
+  const auto on = [&](int tile) { return tile_plan(mode, tile, p, 1, 0); };
+  if (g_tile == 1) return on(T128x160);
+  if (g_tile == 4) return on(T256x160_42);
+  if (mode != MODE_GEGLU_GT && g_tile == 7) return on(T128x160_42);  // sweep: two workgroups per CU
+  if (mode == MODE_GEGLU_GT && g_tile == 0 && !g_gt320 && p.N % 320 == 0 && nt320 >= 240)
     // knob 20 = 0: the same rows on 256x160 tiles, 8 waves 4 x 2 (wave tile 64 x 80)
-    return launch_tile<256, 160, 4, 2, MODE>(p, nullptr, s, 1);
+    return on(T256x160_42);
   if (p.N % 320 == 0 && nt320 >= 240) {
     // 2x4 waves (wave tile 128 rows x 40 neurons): with the row-fastest epilogue its 32-row staging passes are
     // conflict-free (4x2's 16-row passes are not: two 16-lane b128 groups mix column pairs); 174.6 vs 181.2 us at
     // M = 65536, 129.8 vs 132.9 at 16384, 103.4 vs 106.4 at 4096 (same box)
-    if (g_tile == 5) return launch_tile<256, 320, 4, 2, MODE>(p, nullptr, s, 1);
-    return launch_tile<256, 320, 2, 4, MODE>(p, nullptr, s, 1);
+    return on(g_tile == 5 ? T256x320_42 : T256x320);
   }
   // one prompt per call at the 16x16 level (M = 512, N = 10240): 8-wave 128x160 tiles, 20.5 vs 27.3 us on the 4-wave
   // ones (the 32x32 level's M = 2048 measured 24.3 vs 19.0 with them; profiles/r05_b1_geglu_keep_tiles.txt)
-  if constexpr (MODE != MODE_GEGLU_GT)
-    if (p.M <= 1024 && nt160_128 >= 128) return launch_tile<128, 160, 4, 2, MODE>(p, nullptr, s, 1);
-  if (nt160_128 >= 200 || p.M > 2048) return launch_tile<128, 160, 2, 2, MODE>(p, nullptr, s, 1);
-  return launch_tile<64, 160, 2, 2, MODE>(p, nullptr, s, 1);
+  if (mode != MODE_GEGLU_GT && p.M <= 1024 && nt160_128 >= 128) return on(T128x160_42);
+  if (nt160_128 >= 200 || p.M > 2048) return on(T128x160);
+  return on(T64x160);
 }
 
-// Tile rule of the dense modes (GEMM, CONV, CONV_UP, GEMM_LN); the masked modes plan as MODE_GEMM (dispatch).
-template <int MODE>
-Plan choose_tile(const GemmParams& p) {
-  static_assert(!mode_akeep(MODE) && !mode_wmask(MODE), "masked modes take the plain GEMM's plan");
+// Tile rule of the dense modes (GEMM, CONV, CONV_UP, GEMM_LN); the masked modes plan as MODE_GEMM (plan_launch).
+TileRule choose_tile(int mode, const GemmParams& p) {
   const int tm256 = (p.M + 255) / 256;
   // forced tile (sdmoe_tune knob 1): 1 = 128x160, 2 = 64x160, 3 = 256x320 (8 waves), 4 = 256x160 (8 waves)
   if (g_tile == 1) return {T128x160, 0, 0};
@@ -1643,8 +1625,8 @@ Plan choose_tile(const GemmParams& p) {
   if (g_tile == 5 && p.N % 320 == 0) return {T256x320_42, 0, 0};
   if (g_tile == 6 && p.N % 320 == 0) return {T128x320, 0, 0};
   // sweep-only 8-wave tiles with a 32x80 wave tile (two workgroups per CU on a 2-stage ring)
-  if (MODE != MODE_CONV_UP && g_tile == 7 && p.N % 160 == 0) return {T128x160_42, 0, 0};
-  if (MODE != MODE_CONV_UP && g_tile == 8 && p.N % 320 == 0) return {T64x320, 0, 0};
+  if (mode != MODE_CONV_UP && g_tile == 7 && p.N % 160 == 0) return {T128x160_42, 0, 0};
+  if (mode != MODE_CONV_UP && g_tile == 8 && p.N % 320 == 0) return {T64x320, 0, 0};
   // 8-wave 256x320 tile (wave tile 128x80: 2.5x the MFMA work per LDS byte of 64x80) whenever it alone fills
   // the chip; 256x160 8-wave + split-K for long-K problems whose 128x160 grid is under ~1.2 waves of CUs.
   // Measured on MI355X with tools/gemm_bench.py --tile.
@@ -1655,14 +1637,14 @@ Plan choose_tile(const GemmParams& p) {
   // 32x32-level projections (M = 16384): the LayerNorm-folded QKV / Q and the plain (no residual) N = 640 GEMM on
   // 128x320 8-wave tiles (wave tile 64x80, one workgroup per CU): 58.8 vs 62.7 us (QKV, N = 1920), 19.5 vs 22.1 us
   // (N = 640) in a same-box tools/gpu_tile_sweep.sh run; the residual / conv shapes measured neutral or slower there
-  if ((MODE == MODE_GEMM_LN && p.M >= 8192 && p.M <= 16384 && p.N % 320 == 0) ||
-      (MODE == MODE_GEMM && !p.R && p.act == ACT_NONE && p.M >= 8192 && p.M <= 16384 && p.N == 640 && p.K == 640))
+  if ((mode == MODE_GEMM_LN && p.M >= 8192 && p.M <= 16384 && p.N % 320 == 0) ||
+      (mode == MODE_GEMM && !p.R && p.act == ACT_NONE && p.M >= 8192 && p.M <= 16384 && p.N == 640 && p.K == 640))
     return {T128x320, 0, 0};
   if (p.N % 320 == 0 && nt320 >= 180) return {T256x320, 0, 0};
   // 1-1.25 waves of 128x160 tiles (M = 4096 x N = 1280 projections at the 16x16 level): 64x160 tiles double
   // the grid to two workgroups per CU — 15-18 % faster in isolation (tools/gpu_tiles_all.sh). Convs keep their
   // tiles: with the convs included the same-box pipeline A/B measured 0.5 % slower.
-  if ((MODE == MODE_GEMM || MODE == MODE_GEMM_LN) && p.N % 160 == 0 && nt160_128 >= 200 && nt160_128 < 320 &&
+  if ((mode == MODE_GEMM || mode == MODE_GEMM_LN) && p.N % 160 == 0 && nt160_128 >= 200 && nt160_128 < 320 &&
       p.K <= 5120)
     return {T64x160, 0, 0};
   // convs (tools/gemm_bench.py --tile/--stages sweep, same box): the 16x16-level 3x3 convs (M = 4096, N = 1280,
@@ -1670,7 +1652,7 @@ Plan choose_tile(const GemmParams& p) {
   // 256x160 with a 2-way split (the 32x32 level's 1280 -> 640 conv stays on 128x160: 207 vs 221 us); the
   // 64x64 -> 32x32 stride-2 conv (M = 16384, N = 320) on 64x160 tiles at two workgroups per CU: 38 vs 57 us on
   // 128x160 with a 3-stage ring
-  if constexpr (MODE == MODE_CONV) {
+  if (mode == MODE_CONV) {
     // 8x8-level 3x3 convs (M = 1024, K = 9 x 1280 / 9 x 2560): 8-wave 128x160 tiles (wave tile 32x80), 2-stage ring
     // (two workgroups per CU), 8-way split-K: 44.6 / 68.2 us vs 51.2 / 72.8 on 256x160 4x2 waves (tile_sweep.py)
     // At one prompt per call (M = 128: 8 tiles) the fixed 8-way split left 64 workgroups streaming ~23 K-steps each
@@ -1692,16 +1674,16 @@ Plan choose_tile(const GemmParams& p) {
   }
   // (the keep-masked down projection at one prompt, <= 128 tiles of 128x160, runs on 64x160 tiles through the plain
   // rule below: 22.3 vs 29.5 us at the 64x64 level, profiles/r05_b1_geglu_keep_tiles.txt)
-  if (p.N % 160 == 0 && p.K >= 2560 && nt160_128 < 300 && !(MODE == MODE_CONV && p.stride == 2))
+  if (p.N % 160 == 0 && p.K >= 2560 && nt160_128 < 300 && !(mode == MODE_CONV && p.stride == 2))
     return {T256x160_42, 0, 0};
-  if (MODE == MODE_CONV_UP) return {p.N % 160 == 0 ? T128x160 : T128x128, 0, 0};
-  if constexpr (MODE == MODE_CONV)  // conv_out (N = 8 padded channels): a quarter of 128x64's MFMA padding
-    if (p.N <= 32 && g_narrow) return {T128x32, 0, 0};
+  if (mode == MODE_CONV_UP) return {p.N % 160 == 0 ? T128x160 : T128x128, 0, 0};
+  // conv_out (N = 8 padded channels): a quarter of 128x64's MFMA padding
+  if (mode == MODE_CONV && p.N <= 32 && g_narrow) return {T128x32, 0, 0};
   if (p.N <= 64) return {T128x64, 0, 0};
   if (p.N % 160 == 0) {
     // plain GEMMs under ~one wave of 128x160 tiles take 64x160 at any M: the 64x64 level's K = 320 projections at one
     // prompt (M = 8192, N = 320: 128 tiles) 7.8 vs 10.6 us, 8.4 vs 11.8 with the residual (r05_b1_linear_tiles.txt)
-    if (nt160_128 >= 200 || (p.M > 2048 && MODE != MODE_GEMM)) return {T128x160, 0, 0};
+    if (nt160_128 >= 200 || (p.M > 2048 && mode != MODE_GEMM)) return {T128x160, 0, 0};
     return {T64x160, 0, 0};
   }
   const int nt128 = ((p.M + 127) / 128) * ((p.N + 127) / 128);
@@ -1712,53 +1694,72 @@ Plan choose_tile(const GemmParams& p) {
 // the tile a masked mode runs the plain GEMM's plan on: the same one where it is instantiated for the mode, with the
 // keep-masked A operand on the 4x2-wave arrangement of 256x320 (wave tile 64x160: half the A fragments to mask per
 // wave, 61 vs 69 us at M = 65536, N = 320, K = 1280); the split stays the plain GEMM's, so the bits do too
-template <int MODE>
-int masked_tile(int t, const GemmParams& p) {
-  if (mode_akeep(MODE) && t == T256x320) return T256x320_42;
+int masked_tile(int mode, int t, const GemmParams& p) {
+  if (mode_akeep(mode) && t == T256x320) return T256x320_42;
   if (t == T128x320 || t == T128x160_42 || t == T64x320 || t == T128x32) return p.N % 160 == 0 ? T128x160 : T128x128;
   return t;
 }
 
-template <int MODE>
-int launch_plan(int tile, int ksplit, int stages_want, const GemmParams& p, float* ws, hipStream_t s) {
-  switch (tile) {
-    case T128x160: return launch_tile<128, 160, 2, 2, MODE>(p, ws, s, ksplit, stages_want);
-    case T64x160: return launch_tile<64, 160, 2, 2, MODE>(p, ws, s, ksplit, stages_want);
-    case T256x320: return launch_tile<256, 320, 2, 4, MODE>(p, ws, s, ksplit, stages_want);
-    case T256x160_42: return launch_tile<256, 160, 4, 2, MODE>(p, ws, s, ksplit, stages_want);
-    case T256x320_42: return launch_tile<256, 320, 4, 2, MODE>(p, ws, s, ksplit, stages_want);
-    case T128x320: return launch_tile<128, 320, 2, 4, MODE>(p, ws, s, ksplit, stages_want);
-    case T128x64: return launch_tile<128, 64, 2, 2, MODE>(p, ws, s, ksplit, stages_want);
-    case T128x128: return launch_tile<128, 128, 2, 2, MODE>(p, ws, s, ksplit, stages_want);
-    case T64x128: return launch_tile<64, 128, 2, 2, MODE>(p, ws, s, ksplit, stages_want);
-    default: break;
-  }
-  if constexpr (MODE == MODE_GEMM || MODE == MODE_CONV || MODE == MODE_GEMM_LN) {
-    if (tile == T128x160_42) return launch_tile<128, 160, 4, 2, MODE>(p, ws, s, ksplit, stages_want);
-    if (tile == T64x320) return launch_tile<64, 320, 2, 4, MODE>(p, ws, s, ksplit, stages_want);
-  }
-  if constexpr (MODE == MODE_CONV)
-    if (tile == T128x32) return launch_tile<128, 32, 2, 2, MODE>(p, ws, s, ksplit, stages_want);
-  return SDMOE_EUNSUP;
+// plan of a dense or masked launch; masked modes plan as the plain GEMM of the shape
+Plan plan_launch(int mode, const GemmParams& p, bool ws, long ws_floats) {
+  const bool masked = mode_akeep(mode) || mode_wmask(mode);
+  const int pm = masked ? MODE_GEMM : mode;
+  const TileRule r = choose_tile(pm, p);
+  const int ksplit = plan_split(kTile[r.tile], pm, p, ws, ws_floats, r.ks_want);
+  return tile_plan(mode, masked ? masked_tile(mode, r.tile, p) : r.tile, p, ksplit, r.stages_want);
 }
 
-// plan of a dense or masked launch: {tile, split, stages wish}; masked modes plan as the plain GEMM of the shape
-template <int MODE>
-Plan plan_launch(const GemmParams& p, const float* ws, long ws_floats, int* ksplit) {
-  constexpr bool MASKED = mode_akeep(MODE) || mode_wmask(MODE);
-  constexpr int PM = MASKED ? MODE_GEMM : MODE;
-  Plan pl = choose_tile<PM>(p);
-  *ksplit = plan_split(kTile[pl.tile], PM, p, ws, ws_floats, pl.ks_want);
-  if constexpr (MASKED) pl.tile = masked_tile<MODE>(pl.tile, p);
-  return pl;
+// plan of a 3x3 conv: halo tiles where plan_halo takes the shape, else shifted tiles
+Plan plan_conv(const GemmParams& p, bool ws, long ws_floats) {
+  Plan pl;
+  if (plan_halo(p, ws, ws_floats, false, &pl)) return pl;
+  return plan_launch(p.upsample ? MODE_CONV_UP : MODE_CONV, p, ws, ws_floats);
 }
 
-template <int MODE>
-int dispatch(const GemmParams& p, float* ws, long ws_floats, hipStream_t s) {
-  int ksplit = 1;
-  const Plan pl = plan_launch<MODE>(p, ws, ws_floats, &ksplit);
-  return launch_plan<MODE>(pl.tile, ksplit, pl.stages_want, p, ws, s);
+// ---- the launch -----------------------------------------------------------------------------------------------
+template <int MODE, int TILE>
+int launch_kernel(const Plan& pl, const GemmParams& p, dim3 grid, hipStream_t s) {
+  constexpr TileShape t = kTile[TILE];
+  constexpr int NTH = 64 * t.wmw * t.wnw;
+  if constexpr (!built(MODE, TILE)) return SDMOE_EUNSUP;
+  else if constexpr (mode_halo(MODE)) gemm_kernel<t.bm, t.bn, t.wmw, t.wnw, MODE, 4, 32><<<grid, NTH, 0, s>>>(p);
+  else if constexpr (!fits3(t.bm, t.bn, MODE)) gemm_kernel<t.bm, t.bn, t.wmw, t.wnw, MODE, 2, 64><<<grid, NTH, 0, s>>>(p);
+  else if (pl.stages == 2) gemm_kernel<t.bm, t.bn, t.wmw, t.wnw, MODE, 2, 64><<<grid, NTH, 0, s>>>(p);
+  else gemm_kernel<t.bm, t.bn, t.wmw, t.wnw, MODE, 3, 64><<<grid, NTH, 0, s>>>(p);
+  return SDMOE_OK;
 }
+
+// launch_kernel<MODE, tile> at MODE * NTILE + tile
+constexpr int NMODE = MODE_GEGLU_GT + 1;
+using LaunchFn = int (*)(const Plan&, const GemmParams&, dim3, hipStream_t);
+template <int... KEY>
+constexpr std::array<LaunchFn, sizeof...(KEY)> launch_table(std::integer_sequence<int, KEY...>) {
+  return {{&launch_kernel<KEY / NTILE, KEY % NTILE>...}};
+}
+constexpr auto kLaunch = launch_table(std::make_integer_sequence<int, NMODE * NTILE>{});
+
+// Runs a plan: the kernel over ntiles x ksplit workgroups and, for a split, the reduce. ws: the slab workspace.
+int launch(const Plan& pl, GemmParams p, float* ws, hipStream_t s) {
+  const TileShape& t = kTile[pl.tile];
+  if (p.w_bstride && p.rows_per_batch % t.bm) return SDMOE_EUNSUP;  // a tile would straddle two images' weights
+  if (pl.ksplit > 1 && !ws) return SDMOE_EARG;
+  p.ksplit = pl.ksplit; p.kchunk = pl.kchunk; p.kchunk2 = pl.kchunk2; p.mfast = pl.mfast;
+  p.part = pl.ksplit > 1 ? ws : nullptr;
+  p.diag = g_diag; p.res16 = g_res16;
+  p.epi_direct = g_epi_direct == 2 || (g_epi_direct == 1 && p.R == nullptr);  // host-side: a device test of R spilled
+  const dim3 grid(((p.M + t.bm - 1) / t.bm) * ((p.N + t.bn - 1) / t.bn) * pl.ksplit);
+  if (const int st = kLaunch[pl.mode * NTILE + pl.tile](pl, p, grid, s)) return st;
+  SDMOE_CHECK_LAUNCH();
+  if (pl.ksplit > 1) {
+    long nchunk = (long)p.M * (p.N / 8);
+    int g = (int)((nchunk + 255) / 256);
+    if (g > 2048) g = 2048;
+    splitk_reduce_kernel<<<g, 256, 0, s>>>(p);
+    SDMOE_CHECK_LAUNCH();
+  }
+  return SDMOE_OK;
+}
+
 
 // ---- elementwise helpers for the GEMM operands ------------------------------------------------------
 
@@ -1915,6 +1916,48 @@ extern "C" int sdmoe_set_gelu_table(const void* table) {
   return SDMOE_OK;
 }
 
+// ---- entry points: validate -> fill -> plan -> launch -----------------------------------------------------------
+namespace {
+
+// linear-style operands: A [M, K] (row stride lda), W [N, K] (ldw), C [M, N] (ldc), bias / residual R (ldr) or null;
+// SDMOE_ESHAPE when an operand's extent does not fit a buffer descriptor (num_records < OOB)
+int fill_linear(GemmParams& p, const void* A, long lda, const void* W, long ldw, const void* bias, const void* R,
+                long ldr, void* C, long ldc, int M, int N, int K, int act) {
+  p.A = (const half_t*)A; p.lda = lda; p.W = (const half_t*)W; p.ldw = ldw; p.C = (half_t*)C; p.ldc = ldc;
+  p.bias = (const half_t*)bias; p.R = (const half_t*)R; p.ldr = ldr;
+  p.M = M; p.N = N; p.K = K; p.act = act; p.rows_per_batch = 1;
+  const long ab = ((long)(M - 1) * lda + K) * 2, wb = ((long)(N - 1) * ldw + K) * 2;
+  if (ab >= (long)OOB || wb >= (long)OOB) return SDMOE_ESHAPE;
+  p.a_bytes = (int)ab; p.w_bytes = (int)wb;
+  return SDMOE_OK;
+}
+
+// the implicit GEMM of a 3x3 conv (pad 1) of nimg H x W x Cin images, K-steps of a Cin2-channel folded 1x1 shortcut
+// appended (Cin2 = 0: none): everything the planners read
+void conv_shape(GemmParams& p, int nimg, int H, int W, int Cin, int Cin2, int Cout, int stride, int upsample, int act) {
+  const int OH = upsample ? 2 * H : (H - 1) / stride + 1, OW = upsample ? 2 * W : (W - 1) / stride + 1;
+  p.M = nimg * OH * OW; p.N = Cout; p.K = 9 * Cin + Cin2; p.act = act;
+  p.ldw = 9L * Cin + Cin2; p.rows_per_batch = OH * OW;
+  p.H = H; p.Wd = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.stride = stride; p.upsample = upsample;
+}
+
+// conv-style operands of a conv_shape()d p: X [nimg*H*W, Cin] (ldx), the weights, bias, per-image column add, residual R
+// (ldr) or the shortcut input X2 [nimg*H*W, Cin2] (ldx2), each possibly null, Y (ldy); SDMOE_ESHAPE as fill_linear
+int fill_conv(GemmParams& p, const void* X, long ldx, const void* Wt, const void* bias, const void* coladd,
+              long coladd_bstride, const void* R, long ldr, const void* X2, long ldx2, void* Y, long ldy) {
+  p.A = (const half_t*)X; p.lda = ldx; p.W = (const half_t*)Wt; p.C = (half_t*)Y; p.ldc = ldy;
+  p.bias = (const half_t*)bias; p.coladd = (const half_t*)coladd; p.coladd_bstride = coladd_bstride;
+  p.R = (const half_t*)R; p.ldr = ldr; p.A2 = (const half_t*)X2; p.lda2 = ldx2;
+  const long rows = (long)(p.M / p.rows_per_batch) * p.H * p.Wd;
+  const long ab = (rows - 1) * ldx * 2 + (long)p.Cin * 2, wb = (long)p.N * p.ldw * 2;
+  const long a2b = X2 ? (rows - 1) * ldx2 * 2 + (long)(p.K - 9 * p.Cin) * 2 : 0;
+  if (ab >= (long)OOB || wb >= (long)OOB || a2b >= (long)OOB) return SDMOE_ESHAPE;
+  p.a_bytes = (int)ab; p.w_bytes = (int)wb; p.a2_bytes = (int)a2b;
+  return SDMOE_OK;
+}
+
+}  // namespace
+
 extern "C" int sdmoe_linear(const void* A, long lda, const void* W, long ldw, const void* bias,
                             const void* coladd, long coladd_bstride, int rows_per_batch,
                             const void* R, long ldr, void* C, long ldc, int M, int N, int K, int act,
@@ -1924,15 +1967,10 @@ extern "C" int sdmoe_linear(const void* A, long lda, const void* W, long ldw, co
   if (K % 64 || N % 8 || lda % 8 || ldw % 8 || ldc % 8 || (R && ldr % 8)) return SDMOE_ESHAPE;
   if (coladd && rows_per_batch <= 0) return SDMOE_EARG;
   GemmParams p{};
-  p.A = (const half_t*)A; p.lda = lda; p.W = (const half_t*)W; p.ldw = ldw;
-  p.bias = (const half_t*)bias; p.coladd = (const half_t*)coladd; p.coladd_bstride = coladd_bstride;
-  p.R = (const half_t*)R; p.ldr = ldr; p.C = (half_t*)C; p.ldc = ldc;
-  p.M = M; p.N = N; p.K = K; p.act = act;
-  p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
-  const long ab = ((long)(M - 1) * lda + K) * 2, wb = ((long)(N - 1) * ldw + K) * 2;
-  if (ab >= (long)OOB || wb >= (long)OOB) return SDMOE_ESHAPE;
-  p.a_bytes = (int)ab; p.w_bytes = (int)wb;
-  return dispatch<MODE_GEMM>(p, workspace, workspace_floats, (hipStream_t)stream);
+  if (const int st = fill_linear(p, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, act)) return st;
+  p.coladd = (const half_t*)coladd; p.coladd_bstride = coladd_bstride;
+  if (rows_per_batch > 0) p.rows_per_batch = rows_per_batch;
+  return launch(plan_launch(MODE_GEMM, p, workspace, workspace_floats), p, workspace, (hipStream_t)stream);
 }
 
 extern "C" int sdmoe_gn_fold(const void* W, long ldw, int N, int K, const void* bias, const float* scale,
@@ -1956,14 +1994,10 @@ extern "C" int sdmoe_linear_per_image(const void* A, long lda, const void* Wf, l
       M % rows_per_batch || w_bstride % 8 || (colbias && colbias_bstride % 4))
     return SDMOE_ESHAPE;
   GemmParams p{};
-  p.A = (const half_t*)A; p.lda = lda; p.W = (const half_t*)Wf; p.ldw = ldw; p.w_bstride = w_bstride;
-  p.colf = colbias; p.colf_bstride = colbias_bstride;
-  p.R = (const half_t*)R; p.ldr = ldr; p.C = (half_t*)C; p.ldc = ldc;
-  p.M = M; p.N = N; p.K = K; p.act = ACT_NONE; p.rows_per_batch = rows_per_batch;
-  const long ab = ((long)(M - 1) * lda + K) * 2, wb = ((long)(N - 1) * ldw + K) * 2;
-  if (ab >= (long)OOB || wb >= (long)OOB || (long)(M / rows_per_batch) * w_bstride * 2 >= (long)OOB) return SDMOE_ESHAPE;
-  p.a_bytes = (int)ab; p.w_bytes = (int)wb;
-  return dispatch<MODE_GEMM>(p, workspace, workspace_floats, (hipStream_t)stream);
+  if (const int st = fill_linear(p, A, lda, Wf, ldw, nullptr, R, ldr, C, ldc, M, N, K, ACT_NONE)) return st;
+  if ((long)(M / rows_per_batch) * w_bstride * 2 >= (long)OOB) return SDMOE_ESHAPE;
+  p.w_bstride = w_bstride; p.colf = colbias; p.colf_bstride = colbias_bstride; p.rows_per_batch = rows_per_batch;
+  return launch(plan_launch(MODE_GEMM, p, workspace, workspace_floats), p, workspace, (hipStream_t)stream);
 }
 
 extern "C" int sdmoe_linear_masked(const void* A, long lda, const void* keep, const void* W, long ldw,
@@ -1973,44 +2007,52 @@ extern "C" int sdmoe_linear_masked(const void* A, long lda, const void* keep, co
   if (!A || !W || !C || M < 0 || N <= 0 || K <= 0) return SDMOE_EARG;
   if (K % 64 || N % 8 || lda % 8 || ldw % 8 || ldc % 8 || (R && ldr % 8)) return SDMOE_ESHAPE;
   GemmParams p{};
-  p.A = (const half_t*)A; p.lda = lda; p.W = (const half_t*)W; p.ldw = ldw;
-  p.bias = (const half_t*)bias; p.R = (const half_t*)R; p.ldr = ldr; p.C = (half_t*)C; p.ldc = ldc;
-  p.M = M; p.N = N; p.K = K; p.act = ACT_NONE; p.rows_per_batch = 1;
-  const long ab = ((long)(M - 1) * lda + K) * 2, wb = ((long)(N - 1) * ldw + K) * 2;
+  if (const int st = fill_linear(p, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ACT_NONE)) return st;
   const long kb = (long)(K / 64) * M * 8, mb = (long)(K / 64) * N * 8;
-  if (ab >= (long)OOB || wb >= (long)OOB || kb >= (long)OOB || mb >= (long)OOB) return SDMOE_ESHAPE;
-  p.a_bytes = (int)ab; p.w_bytes = (int)wb;
+  if (kb >= (long)OOB || mb >= (long)OOB) return SDMOE_ESHAPE;
   p.keep = (const uint8_t*)keep; p.keep_bytes = keep ? (int)kb : 0;
   p.wmask = (const uint8_t*)wmask; p.wmask_bytes = wmask ? (int)mb : 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (keep && wmask) return dispatch<MODE_KEEPW>(p, workspace, workspace_floats, s);
-  if (keep) return dispatch<MODE_KEEP>(p, workspace, workspace_floats, s);
-  if (wmask) return dispatch<MODE_WMASK>(p, workspace, workspace_floats, s);
-  return dispatch<MODE_GEMM>(p, workspace, workspace_floats, s);
+  const int mode = keep ? (wmask ? MODE_KEEPW : MODE_KEEP) : (wmask ? MODE_WMASK : MODE_GEMM);
+  return launch(plan_launch(mode, p, workspace, workspace_floats), p, workspace, (hipStream_t)stream);
 }
 
 extern "C" int sdmoe_gemm_plan(int mode, int M, int N, int K, int has_residual, int act, long workspace_floats,
                                int* out) {
   if (!out || M <= 0 || N <= 0 || K <= 0 || workspace_floats < 0) return SDMOE_EARG;
-  if (K % 64 || N % 8) return SDMOE_ESHAPE;
+  if (K % 64 || N % 8 || (mode_geglu(mode) && N % 160)) return SDMOE_ESHAPE;
   GemmParams p{};
   p.M = M; p.N = N; p.K = K; p.act = act; p.rows_per_batch = 1;
-  static const half_t dummy[8] = {};
-  p.R = has_residual ? dummy : nullptr;  // (only its presence enters the plan)
-  // a non-null stand-in for the workspace pointer: only its presence and size enter the plan
-  float* ws = workspace_floats > 0 ? reinterpret_cast<float*>(out) : nullptr;
-  int ksplit = 1;
+  p.R = has_residual ? reinterpret_cast<const half_t*>(out) : nullptr;  // (only its presence enters the plan)
   Plan pl;
-  switch (mode) {
-    case MODE_GEMM: pl = plan_launch<MODE_GEMM>(p, ws, workspace_floats, &ksplit); break;
-    case MODE_KEEP: pl = plan_launch<MODE_KEEP>(p, ws, workspace_floats, &ksplit); break;
-    case MODE_WMASK: pl = plan_launch<MODE_WMASK>(p, ws, workspace_floats, &ksplit); break;
-    case MODE_KEEPW: pl = plan_launch<MODE_KEEPW>(p, ws, workspace_floats, &ksplit); break;
-    case MODE_GEMM_LN: pl = plan_launch<MODE_GEMM_LN>(p, nullptr, 0, &ksplit); break;  // (as sdmoe_linear_ln)
-    default: return SDMOE_EUNSUP;
-  }
+  if (mode_geglu(mode)) pl = plan_geglu(mode, p);
+  else if (mode == MODE_GEMM_LN) pl = plan_launch(mode, p, false, 0);  // (as sdmoe_linear_ln)
+  else if (mode == MODE_GEMM || mode_akeep(mode) || mode_wmask(mode))
+    pl = plan_launch(mode, p, workspace_floats > 0, workspace_floats);
+  else return SDMOE_EUNSUP;
   const TileShape& t = kTile[pl.tile];
-  out[0] = t.bm; out[1] = t.bn; out[2] = t.wmw; out[3] = t.wnw; out[4] = ksplit;
+  out[0] = t.bm; out[1] = t.bn; out[2] = t.wmw; out[3] = t.wnw; out[4] = pl.ksplit;
+  return SDMOE_OK;
+}
+
+extern "C" int sdmoe_conv_plan(int nimg, int H, int W, int Cin, int Cin2, int Cout, int stride, int upsample,
+                               int has_residual, int gn, int act, long workspace_floats, int* out) {
+  if (!out || nimg <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin2 < 0 || Cout <= 0 || workspace_floats < 0 ||
+      (Cin2 && has_residual))
+    return SDMOE_EARG;
+  if (Cin % 64 || Cin2 % 64 || Cout % 8) return SDMOE_ESHAPE;
+  // (the folded shortcut and the in-kernel GroupNorm exist for plain stride-1 convs only: sdmoe_conv3x3_sc / _gn)
+  if (!(stride == 1 || stride == 2) || (upsample && stride != 1) || ((Cin2 || gn) && (stride != 1 || upsample)) ||
+      (gn && act != ACT_NONE))
+    return SDMOE_EUNSUP;
+  GemmParams p{};
+  conv_shape(p, nimg, H, W, Cin, Cin2, Cout, stride, upsample, act);
+  p.R = has_residual ? reinterpret_cast<const half_t*>(out) : nullptr;  // (only its presence enters the plan)
+  Plan pl;
+  if (!gn) pl = plan_conv(p, workspace_floats > 0, workspace_floats);
+  else if (!plan_halo(p, workspace_floats > 0, workspace_floats, true, &pl)) return SDMOE_EUNSUP;
+  const TileShape& t = kTile[pl.tile];
+  out[0] = mode_halo(pl.mode); out[1] = t.bm; out[2] = t.bn; out[3] = t.wmw; out[4] = t.wnw;
+  out[5] = pl.bk; out[6] = pl.stages; out[7] = pl.ksplit; out[8] = pl.kchunk; out[9] = pl.kchunk2;
   return SDMOE_OK;
 }
 
@@ -2031,16 +2073,10 @@ extern "C" int sdmoe_linear_geglu(const void* A, long lda, const void* W, long l
   if (score && (esize <= 0 || 40 % esize || ld_score < F / esize)) return SDMOE_ESHAPE;
   if (!(act == ACT_GELU || act == ACT_RELU || act == ACT_NONE || act == ACT_SILU)) return SDMOE_EUNSUP;
   GemmParams p{};
-  p.A = (const half_t*)A; p.lda = lda; p.W = (const half_t*)W; p.ldw = ldw;
-  p.bias = (const half_t*)bias; p.C = (half_t*)P; p.ldc = ldp;
-  p.M = M; p.N = 2 * F; p.K = K; p.act = act; p.rows_per_batch = 1;
+  if (const int st = fill_linear(p, A, lda, W, ldw, bias, nullptr, 0, P, ldp, M, 2 * F, K, act)) return st;
   p.score = (half_t*)score; p.ld_score = ld_score; p.esize = esize;
   if (act == ACT_GELU) p.gelu_tab = sdmoe_gelu_tab_current();
-  const long ab = ((long)(M - 1) * lda + K) * 2, wb = ((long)(2 * F - 1) * ldw + K) * 2;
-  if (ab >= (long)OOB || wb >= (long)OOB) return SDMOE_ESHAPE;
-  p.a_bytes = (int)ab; p.w_bytes = (int)wb;
-  if (p.gelu_tab) return dispatch_geglu<MODE_GEGLU_GT>(p, (hipStream_t)stream);
-  return dispatch_geglu<MODE_GEGLU>(p, (hipStream_t)stream);
+  return launch(plan_geglu(p.gelu_tab ? MODE_GEGLU_GT : MODE_GEGLU, p), p, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int sdmoe_ln_fold(const void* W, long ldw, int N, int K, const void* gamma, const void* beta,
@@ -2060,14 +2096,10 @@ extern "C" int sdmoe_linear_ln(const void* A, long lda, const void* Wf, long ldw
   if (!A || !Wf || !bias_f || !wsum || !C || M < 0 || N <= 0 || K <= 0) return SDMOE_EARG;
   if (K % 64 || N % 8 || lda % 8 || ldw % 8 || ldc % 8) return SDMOE_ESHAPE;
   GemmParams p{};
-  p.A = (const half_t*)A; p.lda = lda; p.W = (const half_t*)Wf; p.ldw = ldw;
-  p.C = (half_t*)C; p.ldc = ldc;
-  p.M = M; p.N = N; p.K = K; p.act = ACT_NONE; p.rows_per_batch = 1;
+  if (const int st = fill_linear(p, A, lda, Wf, ldw, nullptr, nullptr, 0, C, ldc, M, N, K, ACT_NONE)) return st;
   p.ln_wsum = wsum; p.ln_bias = bias_f; p.ln_eps = eps;
-  const long ab = ((long)(M - 1) * lda + K) * 2, wb = ((long)(N - 1) * ldw + K) * 2;
-  if (ab >= (long)OOB || wb >= (long)OOB) return SDMOE_ESHAPE;
-  p.a_bytes = (int)ab; p.w_bytes = (int)wb;
-  return dispatch<MODE_GEMM_LN>(p, nullptr, 0, (hipStream_t)stream);  // no split-K: a tile's K loop sees whole rows
+  // no split-K (no workspace): a tile's K loop sees whole rows
+  return launch(plan_launch(MODE_GEMM_LN, p, false, 0), p, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int sdmoe_linear_geglu_ln(const void* A, long lda, const void* W, long ldw, const float* bias_f,
@@ -2079,15 +2111,10 @@ extern "C" int sdmoe_linear_geglu_ln(const void* A, long lda, const void* W, lon
   if (score && (esize <= 0 || 40 % esize || ld_score < F / esize)) return SDMOE_ESHAPE;
   if (!(act == ACT_GELU || act == ACT_RELU || act == ACT_NONE || act == ACT_SILU)) return SDMOE_EUNSUP;
   GemmParams p{};
-  p.A = (const half_t*)A; p.lda = lda; p.W = (const half_t*)W; p.ldw = ldw;
-  p.C = (half_t*)P; p.ldc = ldp;
-  p.M = M; p.N = 2 * F; p.K = K; p.act = act; p.rows_per_batch = 1;
+  if (const int st = fill_linear(p, A, lda, W, ldw, nullptr, nullptr, 0, P, ldp, M, 2 * F, K, act)) return st;
   p.score = (half_t*)score; p.ld_score = ld_score; p.esize = esize;
   p.ln_wsum = wsum; p.ln_bias = bias_f; p.ln_eps = eps;  // (GELU from erfc here: the LN variant has no table form)
-  const long ab = ((long)(M - 1) * lda + K) * 2, wb = ((long)(2 * F - 1) * ldw + K) * 2;
-  if (ab >= (long)OOB || wb >= (long)OOB) return SDMOE_ESHAPE;
-  p.a_bytes = (int)ab; p.w_bytes = (int)wb;
-  return dispatch_geglu<MODE_GEGLU_LN>(p, (hipStream_t)stream);
+  return launch(plan_geglu(MODE_GEGLU_LN, p), p, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int sdmoe_conv3x3(const void* X, long ldx, int nimg, int H, int W, int Cin,
@@ -2099,22 +2126,9 @@ extern "C" int sdmoe_conv3x3(const void* X, long ldx, int nimg, int H, int W, in
   if (Cin % 64 || Cout % 8 || ldx % 8 || ldy % 8 || (R && ldr % 8)) return SDMOE_ESHAPE;
   if (!(stride == 1 || stride == 2) || (upsample && stride != 1)) return SDMOE_EUNSUP;
   GemmParams p{};
-  int OH, OW;
-  if (upsample) { OH = 2 * H; OW = 2 * W; }
-  else { OH = (H - 1) / stride + 1; OW = (W - 1) / stride + 1; }
-  p.A = (const half_t*)X; p.lda = ldx; p.W = (const half_t*)Wt; p.ldw = 9L * Cin;
-  p.bias = (const half_t*)bias; p.coladd = (const half_t*)coladd; p.coladd_bstride = coladd_bstride;
-  p.R = (const half_t*)R; p.ldr = ldr; p.C = (half_t*)Y; p.ldc = ldy;
-  p.M = nimg * OH * OW; p.N = Cout; p.K = 9 * Cin; p.act = act;
-  p.rows_per_batch = OH * OW;
-  p.H = H; p.Wd = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.stride = stride; p.upsample = upsample;
-  const long ab = ((long)nimg * H * W - 1) * ldx * 2 + (long)Cin * 2, wb = (long)Cout * 9 * Cin * 2;
-  if (ab >= (long)OOB || wb >= (long)OOB) return SDMOE_ESHAPE;
-  p.a_bytes = (int)ab; p.w_bytes = (int)wb;
-  const int hs = try_halo(p, workspace, workspace_floats, (hipStream_t)stream);
-  if (hs >= 0) return hs;
-  if (upsample) return dispatch<MODE_CONV_UP>(p, workspace, workspace_floats, (hipStream_t)stream);
-  return dispatch<MODE_CONV>(p, workspace, workspace_floats, (hipStream_t)stream);
+  conv_shape(p, nimg, H, W, Cin, 0, Cout, stride, upsample, act);
+  if (const int st = fill_conv(p, X, ldx, Wt, bias, coladd, coladd_bstride, R, ldr, nullptr, 0, Y, ldy)) return st;
+  return launch(plan_conv(p, workspace, workspace_floats), p, workspace, (hipStream_t)stream);
 }
 
 extern "C" int sdmoe_conv3x3_sc(const void* X, long ldx, int nimg, int H, int W, int Cin, const void* Wt,
@@ -2125,20 +2139,9 @@ extern "C" int sdmoe_conv3x3_sc(const void* X, long ldx, int nimg, int H, int W,
   if (!X || !Wt || !X2 || !Y || nimg < 0 || H <= 0 || W <= 0 || Cout <= 0 || Cin2 <= 0) return SDMOE_EARG;
   if (Cin % 64 || Cin2 % 64 || Cout % 8 || ldx % 8 || ldx2 % 8 || ldy % 8) return SDMOE_ESHAPE;
   GemmParams p{};
-  p.A = (const half_t*)X; p.lda = ldx; p.W = (const half_t*)Wt; p.ldw = 9L * Cin + Cin2;
-  p.bias = (const half_t*)bias; p.coladd = (const half_t*)coladd; p.coladd_bstride = coladd_bstride;
-  p.C = (half_t*)Y; p.ldc = ldy;
-  p.M = nimg * H * W; p.N = Cout; p.K = 9 * Cin + Cin2; p.act = act;
-  p.rows_per_batch = H * W;
-  p.H = H; p.Wd = W; p.Cin = Cin; p.OH = H; p.OW = W; p.stride = 1; p.upsample = 0;
-  p.A2 = (const half_t*)X2; p.lda2 = ldx2;
-  const long ab = ((long)nimg * H * W - 1) * ldx * 2 + (long)Cin * 2, wb = (long)Cout * p.ldw * 2;
-  const long a2b = ((long)nimg * H * W - 1) * ldx2 * 2 + (long)Cin2 * 2;
-  if (ab >= (long)OOB || wb >= (long)OOB || a2b >= (long)OOB) return SDMOE_ESHAPE;
-  p.a_bytes = (int)ab; p.w_bytes = (int)wb; p.a2_bytes = (int)a2b;
-  const int hs = try_halo(p, workspace, workspace_floats, (hipStream_t)stream);
-  if (hs >= 0) return hs;
-  return dispatch<MODE_CONV>(p, workspace, workspace_floats, (hipStream_t)stream);
+  conv_shape(p, nimg, H, W, Cin, Cin2, Cout, 1, 0, act);
+  if (const int st = fill_conv(p, X, ldx, Wt, bias, coladd, coladd_bstride, nullptr, 0, X2, ldx2, Y, ldy)) return st;
+  return launch(plan_conv(p, workspace, workspace_floats), p, workspace, (hipStream_t)stream);
 }
 
 extern "C" int sdmoe_conv3x3_gn(const void* X, long ldx, int nimg, int H, int W, int Cin, const float* gn_scale,
@@ -2149,23 +2152,14 @@ extern "C" int sdmoe_conv3x3_gn(const void* X, long ldx, int nimg, int H, int W,
   if (!X || !gn_scale || !gn_shift || !Wt || !Y || nimg < 0 || H <= 0 || W <= 0 || Cout <= 0 || Cin2 < 0) return SDMOE_EARG;
   if (Cin % 64 || Cin2 % 64 || Cout % 8 || ldx % 8 || ldy % 8 || (R && ldr % 8) || (X2 && ldx2 % 8)) return SDMOE_ESHAPE;
   if ((X2 != nullptr) != (Cin2 > 0) || (X2 && R)) return SDMOE_EARG;
-  // only the halo tiles apply the GroupNorm in the kernel: the caller falls back to apply + conv on EUNSUP
-  if (!g_halo || g_tile || Cin > 1280 || Cout % 320 || W != 64 || (H * W) % 256) return SDMOE_EUNSUP;
   GemmParams p{};
-  p.A = (const half_t*)X; p.lda = ldx; p.W = (const half_t*)Wt; p.ldw = 9L * Cin + Cin2;
-  p.bias = (const half_t*)bias; p.coladd = (const half_t*)coladd; p.coladd_bstride = coladd_bstride;
-  p.R = (const half_t*)R; p.ldr = ldr; p.C = (half_t*)Y; p.ldc = ldy;
-  p.M = nimg * H * W; p.N = Cout; p.K = 9 * Cin + Cin2; p.act = ACT_NONE;
-  p.rows_per_batch = H * W;
-  p.H = H; p.Wd = W; p.Cin = Cin; p.OH = H; p.OW = W; p.stride = 1; p.upsample = 0;
-  p.A2 = (const half_t*)X2; p.lda2 = ldx2;
+  conv_shape(p, nimg, H, W, Cin, Cin2, Cout, 1, 0, ACT_NONE);
+  // only the halo tiles apply the GroupNorm in the kernel: the caller falls back to apply + conv on EUNSUP
+  Plan pl;
+  if (!plan_halo(p, workspace, workspace_floats, true, &pl)) return SDMOE_EUNSUP;
+  if (const int st = fill_conv(p, X, ldx, Wt, bias, coladd, coladd_bstride, R, ldr, X2, ldx2, Y, ldy)) return st;
   p.gn_scale = gn_scale; p.gn_shift = gn_shift; p.gn_silu = silu;
-  const long ab = ((long)nimg * H * W - 1) * ldx * 2 + (long)Cin * 2, wb = (long)Cout * p.ldw * 2;
-  const long a2b = X2 ? ((long)nimg * H * W - 1) * ldx2 * 2 + (long)Cin2 * 2 : 0;
-  if (ab >= (long)OOB || wb >= (long)OOB || a2b >= (long)OOB) return SDMOE_ESHAPE;
-  p.a_bytes = (int)ab; p.w_bytes = (int)wb; p.a2_bytes = (int)a2b;
-  const int hs = try_halo(p, workspace, workspace_floats, (hipStream_t)stream);
-  return hs >= 0 ? hs : SDMOE_EUNSUP;
+  return launch(pl, p, workspace, (hipStream_t)stream);
 }
 
 extern "C" int sdmoe_groupnorm_apply(const void* X, long ldx, int nimg, int HW, int C, const float* scale,

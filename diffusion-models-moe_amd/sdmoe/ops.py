@@ -130,17 +130,32 @@ def wmask_kmajor(bits, perm=None, out=None):
     return out
 
 
-GEMM_PLAN_MODES = {"plain": 0, "keep": 4, "wmask": 5, "keepw": 6, "ln": 7}
+GEMM_PLAN_MODES = {"plain": 0, "keep": 4, "wmask": 5, "keepw": 6, "ln": 7, "geglu": 3, "geglu_ln": 8, "geglu_gt": 15}
 
 
 def gemm_plan(mode, M, N, K, residual=False, act=ACT_NONE, workspace_floats=WS_FLOATS):
-    """The launch sdmoe_linear / _linear_masked / _linear_ln would make for an M x N x K product (sdmoe_gemm_plan,
-    host-only: no device needed): {"tile": (rows, cols), "waves": (along M, along N), "ksplit": k}."""
+    """The launch sdmoe_linear / _linear_masked / _linear_ln would make for an M x N x K product, or sdmoe_linear_geglu
+    ("geglu"; "geglu_gt" with the registered GELU table) / _geglu_ln for M x 2F x K (N = 2F): {"tile": (rows, cols),
+    "waves": (along M, along N), "ksplit": k}. sdmoe_gemm_plan touches no device memory and launches nothing, but it
+    asks the current device for its CU count, which starts the HIP runtime (256 CUs are assumed without a device)."""
     lib = _lib.load()
     out = (ctypes.c_int * 5)()
     _lib.check(lib.sdmoe_gemm_plan(GEMM_PLAN_MODES[mode], M, N, K, int(bool(residual)), act, workspace_floats, out),
                "sdmoe_gemm_plan")
     return {"tile": (out[0], out[1]), "waves": (out[2], out[3]), "ksplit": out[4]}
+
+
+def conv_plan(nimg, H, W, Cin, Cout, *, Cin2=0, stride=1, upsample=False, residual=False, gn=False, act=ACT_NONE,
+              workspace_floats=WS_FLOATS):
+    """The launch sdmoe_conv3x3 (Cin2 > 0: sdmoe_conv3x3_sc; gn: sdmoe_conv3x3_gn, SdmoeError where it would refuse)
+    would make (sdmoe_conv_plan; queries the CU count as gemm_plan does): {"halo", "tile", "waves", "bk", "stages",
+    "ksplit", "kchunk", "kchunk2"}."""
+    lib = _lib.load()
+    out = (ctypes.c_int * 10)()
+    _lib.check(lib.sdmoe_conv_plan(nimg, H, W, Cin, Cin2, Cout, stride, int(bool(upsample)), int(bool(residual)),
+                                   int(bool(gn)), act, workspace_floats, out), "sdmoe_conv_plan")
+    return {"halo": bool(out[0]), "tile": (out[1], out[2]), "waves": (out[3], out[4]), "bk": out[5], "stages": out[6],
+            "ksplit": out[7], "kchunk": out[8], "kchunk2": out[9]}
 
 
 def linear_masked(x, w, bias=None, *, keep=None, wmask=None, residual=None, out=None):

@@ -234,15 +234,28 @@ int sdmoe_linear_masked(const void* A, long lda, const void* keep, const void* W
                         float* workspace, long workspace_floats, void* stream);
 
 /*
- * sdmoe_gemm_plan — host-only query (no device memory, no launch): the launch sdmoe_linear (mode 0),
- * sdmoe_linear_masked with keep (4), wmask (5) or both (6), or sdmoe_linear_ln (7) would make for an M x N x K
- * product with / without a residual and activation act, given workspace_floats of split-K workspace (0 = none):
+ * sdmoe_gemm_plan — query (no device memory, no launch): the launch sdmoe_linear (mode 0), sdmoe_linear_masked
+ * with keep (4), wmask (5) or both (6), or sdmoe_linear_ln (7) would make for an M x N x K product with / without a
+ * residual and activation act, given workspace_floats of split-K workspace (0 = none), or sdmoe_linear_geglu (3; 15 =
+ * with the registered GELU table) / sdmoe_linear_geglu_ln (8) for M x 2F x K (pass N = 2F):
  * out[0..4] = tile rows, tile columns, waves along M, waves along N, split-K factor. Masked modes take the plain
  * GEMM's plan (its split, hence each output's fp32 summation order), so sdmoe_linear_masked is bit-identical to
  * masking A / W first and calling sdmoe_linear; the tests check that over every U-Net shape. Splits depend on the
- * device's CU count (256 on MI355X, also the value without a device).
+ * current device's CU count: the call queries it, which starts the HIP runtime (256, the MI355X's count, is assumed
+ * while no device answers, so the query also works on a host without a GPU).
  */
 int sdmoe_gemm_plan(int mode, int M, int N, int K, int has_residual, int act, long workspace_floats, int* out);
+
+/*
+ * sdmoe_conv_plan — the same query for the 3x3 convs: the launch sdmoe_conv3x3 (Cin2 = 0), sdmoe_conv3x3_sc
+ * (Cin2 > 0: the folded shortcut's channels; stride 1, no upsample, no residual) or, with gn = 1, sdmoe_conv3x3_gn
+ * would make for nimg H x W x Cin images: out[0..9] = halo tiles (1) or shifted tiles (0), tile rows, tile columns,
+ * waves along M, waves along N, K depth of one LDS ring stage, ring stages, split-K factor, K units per split
+ * (64-deep K-steps; halo: 32-channel slices of the main input), folded-shortcut K-steps per split (halo only).
+ * SDMOE_EUNSUP for gn = 1 on a shape sdmoe_conv3x3_gn refuses. Queries the CU count as sdmoe_gemm_plan does.
+ */
+int sdmoe_conv_plan(int nimg, int H, int W, int Cin, int Cin2, int Cout, int stride, int upsample, int has_residual,
+                    int gn, int act, long workspace_floats, int* out);
 
 /*
  * sdmoe_wmask_kmajor — packed Wanda bits [N][K/8] (row stride ldb bytes; bit k%8 of byte (n, k/8) = W[n, k] removed;

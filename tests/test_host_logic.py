@@ -42,6 +42,43 @@ def test_abi_argument_validation_without_gpu():
     assert lib.sdmoe_geglu_route(1, 8, 4, 16, 300, 4, 2, 1, 1, 1, None, 1, 16, None, 0, None, None, None) == -3
     assert lib.sdmoe_geglu_route(1, 8, 4, 16, 8, 9, 2, 1, 1, 1, None, 1, 16, None, 0, None, None, None) == -1
     assert lib.sdmoe_tune(0, 5) == -1 and lib.sdmoe_tune(0, 0) == 0
+    # the GEMM / conv entry points share their operand setup: an operand past the 2 GiB a buffer descriptor spans is a
+    # shape error, and the order in which the codes win is part of the ABI (alignment before the coladd argument
+    # check; sdmoe_conv3x3_gn refuses an unfusable shape before it looks at operand sizes)
+    big = 1 << 20
+    assert lib.sdmoe_linear(1, 2048, 1, 64, None, None, 0, 0, None, 0, 1, 8, big, 8, 64, 0, None, 0, None) == -2
+    assert lib.sdmoe_linear(1, 64, 1, 64, None, 1, 8, 0, None, 0, 1, 8, 4, 8, 64, 0, None, 0, None) == -1
+    assert lib.sdmoe_linear(1, 60, 1, 64, None, 1, 8, 0, None, 0, 1, 8, 4, 8, 64, 0, None, 0, None) == -2
+    assert lib.sdmoe_linear_per_image(1, 64, 1, 64, 1 << 29, None, 0, 256, None, 0, 1, 8, 1024, 8, 64, None, 0, None) == -2
+    assert lib.sdmoe_linear_masked(1, 64, 1, 1, 64, None, None, None, 0, 1, 8, 1 << 22, 8, 4096, None, 0, None) == -2
+    assert lib.sdmoe_linear_geglu(1, 64, 1, 64, 1, 1, 80, 4, 80, 64, 4, None, 0, 0, None) == -3
+    assert lib.sdmoe_linear_geglu(1, big, 1, 64, 1, 1, 80, 4096, 80, 64, 3, None, 0, 0, None) == -2
+    assert lib.sdmoe_linear_ln(1, big, 1, 64, 1, 1, 1e-5, 1, 8, 4096, 8, 64, None) == -2
+    assert lib.sdmoe_linear_geglu_ln(1, 64, 1, 1 << 26, 1, 1, 1e-5, 1, 80, 4, 80, 64, 3, None, 0, 0, None) == -2
+    assert lib.sdmoe_conv3x3(1, 8192, 64, 64, 64, 64, 1, None, None, 0, None, 0, 1, 8, 8, 1, 0, 0, None, 0, None) == -2
+    assert lib.sdmoe_conv3x3_sc(1, 64, 2, 8, 8, 64, 1, None, None, 0, 1, 1 << 26, 64, 1, 8, 8, 0, None, 0, None) == -2
+
+    def gn(ldx, nimg, hw, cin, r, x2, cin2, cout):
+        return lib.sdmoe_conv3x3_gn(1, ldx, nimg, hw, hw, cin, 1, 1, 1, 1, None, None, 0, r, 320, x2, 64, cin2, 1, 320,
+                                    cout, None, 0, None)
+
+    assert gn(8192, 64, 32, 64, None, None, 0, 320) == -3   # 32-wide: not fusable (and too large)
+    assert gn(8192, 64, 64, 64, None, None, 0, 320) == -2   # fusable, too large
+    assert gn(64, 2, 64, 1344, None, None, 0, 320) == -3    # more channels than the kernel stages scale / shift for
+    assert gn(64, 2, 64, 64, None, None, 0, 328) == -3
+    assert gn(64, 2, 64, 64, None, 1, 0, 320) == -1         # a shortcut input without shortcut channels
+    assert gn(64, 2, 64, 64, 1, 1, 64, 320) == -1           # shortcut and residual together
+    # the plan queries
+    out = (ctypes.c_int * 10)()
+    assert lib.sdmoe_gemm_plan(3, 512, 200, 64, 0, 0, 0, out) == -2 and lib.sdmoe_gemm_plan(9, 512, 320, 64, 0, 0, 0, out) == -3
+    assert lib.sdmoe_gemm_plan(15, 512, 320, 64, 0, 2, 0, None) == -1
+    assert lib.sdmoe_conv_plan(2, 64, 64, 64, 0, 320, 1, 0, 0, 0, 0, 0, None) == -1
+    assert lib.sdmoe_conv_plan(2, 64, 64, 64, 64, 320, 1, 0, 1, 0, 0, 0, out) == -1
+    assert lib.sdmoe_conv_plan(2, 64, 64, 32, 0, 320, 1, 0, 0, 0, 0, 0, out) == -2
+    assert lib.sdmoe_conv_plan(2, 64, 64, 64, 0, 320, 3, 0, 0, 0, 0, 0, out) == -3
+    assert lib.sdmoe_conv_plan(2, 64, 64, 64, 64, 320, 2, 0, 0, 0, 0, 0, out) == -3
+    assert lib.sdmoe_conv_plan(2, 32, 32, 64, 0, 320, 1, 0, 0, 1, 0, 0, out) == -3
+    assert lib.sdmoe_conv_plan(2, 64, 64, 64, 0, 320, 1, 0, 0, 1, 0, 0, out) == 0 and list(out)[:3] == [1, 128, 320]
 
 
 def test_ops_refuse_cpu_tensors():
@@ -603,3 +640,136 @@ def test_masked_gemm_plans_take_the_plain_split():
     # without a workspace nothing splits; sdmoe_linear_ln never splits
     assert ops.gemm_plan("plain", 128, 1280, 5120, workspace_floats=0)["ksplit"] == 1
     assert ops.gemm_plan("ln", 128, 1280, 1280)["ksplit"] == 1
+    # the tile of a masked mode is the one masked_tile() (csrc/gemm.hip) maps the plain tile to: the same tile, except
+    # that the tiles not built for the masked modes (128x320, 64x320, 8-wave 128x160, 128x32) fall to 128x160 (N % 160
+    # == 0) or 128x128, and the keep-masked A operand runs 256x320 on 4x2 waves. Every one walks K in 64-deep steps.
+    from sdmoe import _lib
+    lib = _lib.load()
+
+    def expect(mode, plain, N):
+        tile, waves = plain["tile"], plain["waves"]
+        if mode in ("keep", "keepw") and (tile, waves) == ((256, 320), (2, 4)):
+            return (256, 320), (4, 2)
+        if tile in ((128, 320), (64, 320), (128, 32)) or (tile, waves) == ((128, 160), (4, 2)):
+            return ((128, 160) if N % 160 == 0 else (128, 128)), (2, 2)
+        return tile, waves
+
+    seen = set()
+    try:
+        for knob1, M, N, K in ((0, 16384, 640, 640), (0, 8192, 640, 640), (8, 4096, 320, 1280), (8, 512, 640, 640),
+                               (7, 2048, 320, 1280), (0, 65536, 320, 1280), (0, 65536, 640, 2560), (0, 1000, 1280, 5120)):
+            assert lib.sdmoe_tune(1, knob1) == 0
+            plain = ops.gemm_plan("plain", M, N, K)
+            seen.add((plain["tile"], plain["waves"]))
+            for mode in ("keep", "wmask", "keepw"):
+                got = ops.gemm_plan(mode, M, N, K)
+                assert (got["tile"], got["waves"]) == expect(mode, plain, N), (mode, knob1, M, N, K, got, plain)
+                assert got["ksplit"] == plain["ksplit"]
+    finally:
+        lib.sdmoe_tune(1, 0)
+    assert {((128, 320), (2, 4)), ((64, 320), (2, 4)), ((256, 320), (2, 4)), ((128, 160), (4, 2))} <= seen
+
+
+def _launch_plan_table():
+    with open(os.path.join(os.path.dirname(__file__), "golden", "launch_plans.json")) as f:
+        return json.load(f)
+
+
+def _plan10(p):
+    return [int(p["halo"]), *p["tile"], *p["waves"], p["bk"], p["stages"], p["ksplit"], p["kchunk"], p["kchunk2"]]
+
+
+# the conv grid of the plan tests: H = W, images, input / output channels (every halo width and row count, odd sizes,
+# narrow outputs), crossed with the ways a conv is issued
+_GRID_HW = (8, 10, 16, 24, 32, 48, 64, 96)
+_GRID_NIMG = (1, 2, 3, 4, 8, 16, 32)
+_GRID_CIN = (64, 128, 320, 640, 960, 1280, 1920, 2560)
+_GRID_COUT = (8, 32, 64, 320, 640, 1280)
+_GRID_KIND = (dict(), dict(stride=2), dict(upsample=True), dict(residual=True), dict(Cin2=320), dict(Cin2=640))
+
+
+def test_conv_and_geglu_launch_plans():
+    """Every launch is a plan and plans are observable on the host (sdmoe_conv_plan, sdmoe_gemm_plan's GEGLU modes).
+    The plans of the 3x3 convs and routed GEGLU projections SD-1.4 and SDXL issue at 1 / 2 / 8 / 16 prompts per call
+    equal tests/golden/launch_plans.json, which was recorded at the kernel launch sites of the revision before the
+    planners existed (256 CUs, the default workspace), so a change of any tile, ring depth or split shows here; and the
+    split invariants hold over a grid of conv shapes and workspace sizes."""
+    from unet_shapes import conv3x3_shapes, geglu_projection_shapes
+    from sdmoe import ops, _lib
+    table = _launch_plan_table()
+    convs = conv3x3_shapes("sd14") + conv3x3_shapes("sdxl")
+    assert (32, 64, 320, 0, 320, 1, 0, 0) in convs      # 64x64 320 -> 320 at 32 images
+    assert (2, 16, 2560, 0, 1280, 1, 0, 0) in convs     # 16x16 2560 -> 1280 at one prompt
+    assert (2, 8, 1280, 0, 1280, 1, 1, 0) in convs      # the 8 -> 16 upsample at one prompt
+    geglus = geglu_projection_shapes("sd14") + geglu_projection_shapes("sdxl")
+    assert (512, 5120, 1280) in geglus
+    assert sorted(set(convs)) == sorted(tuple(c[0]) for c in table["conv"])
+    assert sorted(set(geglus)) == sorted({tuple(g[1:4]) for g in table["geglu"]})
+    for (nimg, H, Cin, Cin2, Cout, stride, up, res), plain, gn in table["conv"]:
+        kw = dict(Cin2=Cin2, stride=stride, upsample=up, residual=res)
+        assert _plan10(ops.conv_plan(nimg, H, H, Cin, Cout, **kw)) == plain, (nimg, H, Cin, Cout, kw)
+        if gn is not None:
+            assert _plan10(ops.conv_plan(nimg, H, H, Cin, Cout, gn=True, **kw)) == gn, (nimg, H, Cin, Cout, kw)
+        else:
+            with pytest.raises(_lib.SdmoeError, match="unsupported mode"):
+                ops.conv_plan(nimg, H, H, Cin, Cout, gn=True, **kw)
+    for mode, M, F, K, want in table["geglu"]:
+        p = ops.gemm_plan(mode, M, 2 * F, K)
+        assert [*p["tile"], *p["waves"], p["ksplit"]] == want, (mode, M, F, K)
+
+    lib = _lib.load()
+    out = (ctypes.c_int * 10)()
+
+    def grid_plans(ws):
+        for H in _GRID_HW:
+            for nimg in _GRID_NIMG:
+                for Cin in _GRID_CIN:
+                    for Cout in _GRID_COUT:
+                        for kind in _GRID_KIND:
+                            st = lib.sdmoe_conv_plan(nimg, H, H, Cin, kind.get("Cin2", 0), Cout, kind.get("stride", 1),
+                                                     int(kind.get("upsample", False)), int(kind.get("residual", False)),
+                                                     0, 0, ws, out)
+                            assert st == 0, (st, nimg, H, Cin, Cout, kind)
+                            yield nimg, H, Cin, Cout, kind, list(out)
+
+    for ws in (0, 1 << 20, ops.WS_FLOATS):
+        nhalo = 0
+        for nimg, H, Cin, Cout, kind, (halo, bm, bn, wmw, wnw, bk, stages, ksplit, kchunk, kchunk2) in grid_plans(ws):
+            what = (ws, nimg, H, Cin, Cout, kind)
+            OH = 2 * H if kind.get("upsample") else (H - 1) // kind.get("stride", 1) + 1
+            M = nimg * OH * OH
+            # the slabs of a split fit the workspace; nothing splits without one
+            assert ksplit >= 1 and (ksplit == 1 or ksplit * M * Cout <= ws) and (ws > 0 or ksplit == 1), what
+            units = Cin // 32 if halo else (9 * Cin + kind.get("Cin2", 0)) // 64  # what kchunk counts
+            assert (ksplit - 1) * kchunk < units <= ksplit * kchunk, what
+            if halo:
+                nhalo += 1
+                assert Cout % 320 == 0 and bn == 320 and (OH * OH) % bm == 0 and (bk, stages) == (32, 4), what
+                assert ksplit * kchunk2 >= kind.get("Cin2", 0) // 32, what
+            else:
+                assert bk == 64 and stages in (2, 3) and kchunk2 == 0, what
+        assert nhalo > 1000
+    try:
+        assert lib.sdmoe_tune(16, 0) == 0
+        assert not any(p[0] for *_, p in grid_plans(ops.WS_FLOATS))
+    finally:
+        lib.sdmoe_tune(16, 1)
+
+
+def test_conv_gn_fusable_agrees_with_the_library(monkeypatch):
+    """ops.conv_gn_fusable (the per-layer Python check that decides between the fused GroupNorm conv and the apply
+    pass) states the same condition as the library: sdmoe_conv_plan with gn = 1 succeeds exactly where it is true."""
+    from sdmoe import ops, _lib
+    monkeypatch.setattr(ops, "FUSED_GN", True)
+    lib = _lib.load()
+    out = (ctypes.c_int * 10)()
+    ntrue = 0
+    for H in _GRID_HW:
+        for W in (H, 64):
+            for Cin in _GRID_CIN:
+                for Cout in _GRID_COUT:
+                    st = lib.sdmoe_conv_plan(2, H, W, Cin, 0, Cout, 1, 0, 0, 1, 0, ops.WS_FLOATS, out)
+                    assert st in (0, -3), st
+                    assert ops.conv_gn_fusable(H, W, Cin, Cout) == (st == 0), (H, W, Cin, Cout, st)
+                    ntrue += st == 0
+    assert ntrue > 20
