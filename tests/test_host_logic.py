@@ -773,3 +773,29 @@ def test_conv_gn_fusable_agrees_with_the_library(monkeypatch):
                     assert ops.conv_gn_fusable(H, W, Cin, Cout) == (st == 0), (H, W, Cin, Cout, st)
                     ntrue += st == 0
     assert ntrue > 20
+
+
+def test_forced_split_counts_leave_no_empty_split():
+    """A forced split count (sdmoe_tune knob 9) ks on nk K-steps is clamped to nk, gives ceil(nk / ks) K-steps per
+    split and as many splits as that takes: ceil(nk / ceil(nk / min(ks, nk))) -- the count tests/test_gpu_launch_space.py
+    expects of every forced launch. A workspace of s slabs lowers the wanted count to s first, so never more than s
+    splits come out."""
+    from sdmoe import ops, _lib
+    lib = _lib.load()
+
+    def splits(nk, ks):
+        kchunk = -(-nk // min(ks, nk))
+        return -(-nk // kchunk)
+
+    M, N = 64, 320
+    try:
+        for ks in range(1, 33):
+            assert lib.sdmoe_tune(9, ks) == 0
+            for nk in range(1, 25):
+                assert ops.gemm_plan("plain", M, N, 64 * nk)["ksplit"] == splits(nk, ks), (nk, ks)
+                for s in (1, 2, 3, 4, 7, 11, 24):
+                    got = ops.gemm_plan("plain", M, N, 64 * nk, workspace_floats=s * M * N)["ksplit"]
+                    assert got <= s and got == splits(nk, min(ks, s)), (nk, ks, s, got)
+                assert ops.gemm_plan("plain", M, N, 64 * nk, workspace_floats=0)["ksplit"] == 1
+    finally:
+        lib.sdmoe_tune(9, 0)
