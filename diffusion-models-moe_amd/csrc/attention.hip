@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "tune.h"
 #include "../../include/sdmoe.h"
 
 namespace {
@@ -599,30 +600,28 @@ __global__ __launch_bounds__(NW * 64, (D >= 160 || NW >= 8 ? 1 : 2)) void attn32
     }
 }
 
-// sdmoe_tune knob 4: 0 = by shape (default): attn32_kernel for d = 80 self-attention (Nk > 128), the 16x16x32 kernel
-// in 8-wave workgroups for d = 40 / 64 self-attention (Nk > 128), the 4-wave 16x16x32 kernel (NQF = 2) everywhere
-// else; 1 = attn32_kernel; 2 or 4 = the 4-wave 16x16x32 kernel with NQF = 2 / 4; 8 = the 16x16x32 kernel in
-// 8-wave workgroups (d <= 80); 9 = attn32_kernel in 8-wave workgroups (d <= 80)
-int g_attn_nqf = 0;
-
+// kernel by shape, or the one KNOB_ATTN forces (values in include/sdmoe.h): attn32_kernel for d = 80 self-attention
+// (Nk > 128), the 16x16x32 kernel in 8-wave workgroups for d = 40 / 64 self-attention (Nk > 128), the 4-wave 16x16x32
+// kernel (NQF = 2) everywhere else
 template <int D>
 int launch(const AttnParams& p, int nimg, hipStream_t s) {
-  // 64 queries per wave (NQF = 4) only on request (knob 4): at d = 40, N = 4096 it measured equal to NQF = 2
+  const int forced = knob(KNOB_ATTN);
+  // 64 queries per wave (NQF = 4) only on request: at d = 40, N = 4096 it measured equal to NQF = 2
   // (500 us both; 232 vs 128 VGPRs halves the waves per SIMD) and 12 % slower on the 77-key cross-attention;
   // head dims above 40 would spill at NQF = 4 (64: 16 VGPRs, 80: 130)
   constexpr bool WIDE_OK = D <= 40;
-  const bool wide = g_attn_nqf == 4;
+  const bool wide = forced == 4;
   // same-box timings, 16 images x 8 heads, 16x16x32 vs 32x32x16 (us): d = 40 N = 4096 self 499 vs 524, 77-key cross
   // 34.1 vs 41.0; d = 64 N = 4096 630 vs 645, cross 43.4 vs 50.8; d = 80 N = 1024 self 66.9 vs 64.0 (the contraction
   // 80 -> 80 instead of 96), cross 21.4 vs 22.2; d = 160 19.2 vs 19.5. The 32x32x16 loop issues fewer instructions
   // (14 MFMAs and ~100 VALU per 64-key tile vs 28 and ~110 at d = 40) but runs slower: lower clock under DVFS for
   // the 32x32 MFMA (MI355X_MICROARCH.md) and 2-way LDS bank conflicts on its V^T transpose reads (row stride 56)
-  const bool use32 = g_attn_nqf == 1 || (g_attn_nqf == 0 && D == 80 && p.Nk > 128);
+  const bool use32 = forced == 1 || (forced == 0 && D == 80 && p.Nk > 128);
   // 8-wave workgroups (256 queries share each K/V tile: half the LDS-DMA pieces per wave and tile) for the long
   // self-attentions at d = 40 / 64: d = 40 N = 4096 448 vs 464-475 us, pipeline +0.5 % (same box); slower on the
   // 77-key cross-attention (34.4 vs 31.1 us: fewer workgroups) and at d = 80 (65.4 vs 62.4 us with attn32)
-  const bool use8 = g_attn_nqf == 8 || (g_attn_nqf == 0 && (D == 40 || D == 64) && p.Nk > 128);
-  if (g_attn_nqf == 9 && D <= 80) {  // 32x32x16 kernel in 8-wave workgroups
+  const bool use8 = forced == 8 || (forced == 0 && (D == 40 || D == 64) && p.Nk > 128);
+  if (forced == 9 && D <= 80) {  // 32x32x16 kernel in 8-wave workgroups
     dim3 grid((p.Nq + 255) / 256, p.heads, nimg);
     attn32_kernel<D, (D <= 80 ? 8 : 4)><<<grid, (D <= 80 ? 512 : 256), 0, s>>>(p);
   } else if (use32) {
@@ -643,12 +642,6 @@ int launch(const AttnParams& p, int nimg, hipStream_t s) {
 }
 
 }  // namespace
-
-int sdmoe_attn_set_nqf(int v) {
-  if (v != 0 && v != 1 && v != 2 && v != 4 && v != 8 && v != 9) return SDMOE_EARG;
-  g_attn_nqf = v;
-  return SDMOE_OK;
-}
 
 extern "C" int sdmoe_attention(const void* Q, long ldq, const void* K, long ldk, const void* V, long ldv,
                                void* O, long ldo, int nimg, int Nq, int Nk, int heads, int head_dim,

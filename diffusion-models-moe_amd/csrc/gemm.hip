@@ -21,25 +21,12 @@
 #include <utility>
 
 #include "common.h"
+#include "tune.h"
 #include "../../include/sdmoe.h"
 
 namespace {
 
 constexpr int BK = 64;
-
-// tuning knobs (sdmoe_tune): 0 = LDS stages (0 = auto, 2 or 3); 1 = forced tile config (0 = auto)
-int g_stages = 0;
-int g_tile = 0;
-int g_res16 = 1;  // knob 8: 1 = residual epilogues on the fp16 staging path (residual added in the copy-out), 0 = fp32
-int g_ksplit = 0;  // knob 9: forced split-K factor (0 = auto; 1 = never split), for tile sweeps
-int g_mfast = 1;   // knob 14: split-K conv grids ordered M-tile fastest (1) or split fastest (0)
-// knob 23: fp16 epilogues storing 16-B row pieces straight from the fragments (no LDS staging): 1 (default) = when
-// there is no residual (LN-folded projections 4-12 %, plain K = 320 linears ~3 % faster; with a residual its 16-B
-// residual loads measured 3-7 % slower than the staged copy-out), 2 = always, 0 = never
-int g_epi_direct = 1;
-int g_diag = 0;  // knob 6, diagnostics only (results garbage): bit 0 = no K-loop operand loads, bit 1 = no MFMAs,
-                 // bit 4 = no A-operand pieces, bit 5 = no B-operand pieces,
-                 // bit 2 = no epilogue (nothing stored), bit 3 = epilogue without its global stores
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 
@@ -66,7 +53,7 @@ struct GemmParams {
   half_t* score; long ld_score;
   int esize;
   int res16;  // residual on the fp16 staging path (sdmoe_tune knob 8)
-  int diag;  // diagnostic knob (sdmoe_tune 6): bit 0 skips the K-loop loads, bit 1 the MFMAs
+  int diag;  // diagnostics bits (sdmoe_tune knob 6, results garbage)
   int epi_direct;  // fp16 epilogue: stores straight from the fragments instead of LDS staging (knob 23 policy)
   // expert keep mask of the A operand (MODE_KEEP / MODE_KEEPW): keep[(k / 64) * M * 8 + m * 8 + (k % 64) / 8] bit
   // (k % 8) = neuron k of token m survives the top-k; the A fragments are ANDed with it after their LDS read
@@ -97,7 +84,7 @@ struct GemmParams {
   const float* gn_scale; const float* gn_shift; int gn_silu;
 };
 
-SDMOE_DEV bool g_res16_dev(const GemmParams& p) { return p.res16 != 0; }
+SDMOE_DEV bool res16_dev(const GemmParams& p) { return p.res16 != 0; }
 
 constexpr unsigned OOB = 0x80000000u;  // > every num_records used here (tensors < 2 GiB)
 
@@ -1033,7 +1020,7 @@ __global__ __launch_bounds__(64 * WMW * WNW, (NSTAGE == 2 && (WMW * WNW == 4 || 
   }
   __syncthreads();
   constexpr int CPR = WN / 8;
-  if (!GEGLU && p.act == ACT_NONE && (!p.R || g_res16_dev(p))) {
+  if (!GEGLU && p.act == ACT_NONE && (!p.R || res16_dev(p))) {
     // fp16 path: bias and per-image column add in registers on each lane's 4-column row piece (one rounding, as
     // epilogue8), staged as fp16 (one ds_write_b64 per fragment: 1/2.5 of the LDS time of staging fp32 with 4
     // ds_write_b32), then copied out in 16-B row chunks: 175 -> 166 us for the M = 65536, N = 2560, K = 320 linear,
@@ -1445,8 +1432,9 @@ int plan_split(const TileShape& t, int mode, const GemmParams& p, bool ws, long 
   const int cus = device_cus();
   int ksplit = 1;
   // fill the chip: split K when the tile grid covers well under one wave of CUs
-  if (ws && (g_ksplit > 0 || ks_want > 0)) {
-    ksplit = g_ksplit > 0 ? g_ksplit : ks_want;
+  const int forced = knob(KNOB_KSPLIT);
+  if (ws && (forced > 0 || ks_want > 0)) {
+    ksplit = forced > 0 ? forced : ks_want;
     if (ksplit > nk) ksplit = nk;
   } else if (ws && (mode == MODE_CONV || mode == MODE_CONV_UP) && ntiles <= 16 && nk >= 64) {
     // latency regime (one prompt per call, base_receiver.py:73: 8x8 / 16x16 / 32x32 convs at batch 2): up to two
@@ -1481,22 +1469,21 @@ Plan tile_plan(int mode, int tile, const GemmParams& p, int ksplit, int stages_w
   // M-fastest order for split-K convs only: their weight slices (up to 29 MB at the 16x16 level) were re-fetched by
   // every XCD (PMC FETCH_SIZE of the split-K conv launches 140 -> 46 MB, time neutral); the M = 1024 split-K linears
   // measured 2 us slower with it
-  pl.mfast = (pl.ksplit > 1 && g_mfast && (mode == MODE_CONV || mode == MODE_CONV_UP)) ? 1 : 0;
+  pl.mfast = (pl.ksplit > 1 && knob(KNOB_MFAST) && (mode == MODE_CONV || mode == MODE_CONV_UP)) ? 1 : 0;
   // 64-deep K-steps (a 32-deep 4/5-stage ring measured slower on every shape; the kernel is generic in BK).
   // 4-wave tiles: 2-stage ring (2 workgroups/CU) when the grid has >= ~300 workgroups, else 3-stage; 8-wave
   // tiles: 3-stage where it fits in LDS -- measured crossovers on MI355X.
-  const int stages = g_stages ? g_stages
-                              : (stages_want ? stages_want : ((t.wmw * t.wnw == 4 && ntiles * pl.ksplit >= 300) ? 2 : 3));
+  const int stages = knob(KNOB_STAGES) ? knob(KNOB_STAGES)
+                                       : (stages_want ? stages_want : ((t.wmw * t.wnw == 4 && ntiles * pl.ksplit >= 300) ? 2 : 3));
   pl.stages = (stages == 2 || !fits3(t.bm, t.bn, mode)) ? 2 : 3;
   return pl;
 }
 
-// knob 16: halo-tiled stride-1 3x3 convs: 1 (default) = where they measured faster than the shifted-tile kernel:
-// 64-wide outputs (256-row tiles), 16-wide ones on 256-row tiles (a whole image), the 32 -> 64, 16 -> 32 (256-row
-// tiles) and 8 -> 16 upsample convs, 32-wide outputs with Cin >= 1280 (256-row tiles); 2 = every 128-row tile instead
-// (32- / 16-wide outputs: 5-17 % slower, their 32-deep K-steps carry half the MFMAs per barrier); 3 = the default plus
-// every 32-wide output on 256-row tiles (135.1 vs 118.0 us at 640 -> 640); 0 = off
-int g_halo = 1;
+// Halo policy (KNOB_HALO, values in include/sdmoe.h): the default takes halo tiles where they measured faster than the
+// shifted-tile kernel: 64-wide outputs (256-row tiles), 16-wide ones on 256-row tiles (a whole image), the 32 -> 64,
+// 16 -> 32 (256-row tiles) and 8 -> 16 upsample convs, 32-wide outputs with Cin >= 1280 (256-row tiles). Every 128-row
+// tile instead (2) ran 5-17 % slower on 32- / 16-wide outputs (their 32-deep K-steps carry half the MFMAs per barrier);
+// every 32-wide output on 256-row tiles (3) 135.1 vs 118.0 us at 640 -> 640.
 
 // the plan of a halo conv on tile (BM x 320, 8 waves 2 x 4, BK 32, 4-slot B ring): K split over whole 32-channel slices
 // when the tile grid is under ~one wave of CUs
@@ -1505,8 +1492,9 @@ Plan halo_plan(int tile, int mode, const GemmParams& p, bool ws, long ws_floats)
   const int ntiles = (p.M / kTile[tile].bm) * (p.N / 320);
   const int nsl = p.Cin / 32;
   int ksplit = 1;
-  if (ws && g_ksplit > 0) {  // forced (knob 9, sweeps): at most one 32-channel slice per split
-    ksplit = g_ksplit < nsl ? g_ksplit : nsl;
+  const int forced = knob(KNOB_KSPLIT);
+  if (ws && forced > 0) {  // sweeps: at most one 32-channel slice per split
+    ksplit = forced < nsl ? forced : nsl;
   } else if (ws && ntiles <= 32) {
     // latency regime (batch 2: whole 16x16 images, the 8 -> 16 upsample, 64x64 at 32 tiles): up to two workgroups
     // per CU, >= 2 slices per split, <= 96 MB of fp32 slabs -- B = 1 sweep: 16x16 1280 -> 1280 56.1 -> 40.9 us
@@ -1530,7 +1518,7 @@ Plan halo_plan(int tile, int mode, const GemmParams& p, bool ws, long ws_floats)
   pl.kchunk = (nsl + ksplit - 1) / ksplit;
   pl.ksplit = (nsl + pl.kchunk - 1) / pl.kchunk;
   pl.kchunk2 = ((p.K - 9 * p.Cin) / 32 + pl.ksplit - 1) / pl.ksplit;
-  pl.mfast = pl.ksplit > 1 ? g_mfast : 0;
+  pl.mfast = pl.ksplit > 1 ? knob(KNOB_MFAST) : 0;
   return pl;
 }
 
@@ -1539,7 +1527,8 @@ Plan halo_plan(int tile, int mode, const GemmParams& p, bool ws, long ws_floats)
 // GroupNorm to its staged input (sdmoe_conv3x3_gn), which only the 64-wide tiles over whole 256-row groups do, for up
 // to the kernel's GN_MAXC = 1280 channels of fp32 scale + shift in LDS
 bool plan_halo(const GemmParams& p, bool ws, long ws_floats, bool gn, Plan* pl) {
-  if (!g_halo || g_tile || p.stride != 1 || p.N % 320 || p.Cin % 32 || (p.K - 9 * p.Cin) % 32) return false;
+  const int halo = knob(KNOB_HALO);
+  if (!halo || knob(KNOB_TILE) || p.stride != 1 || p.N % 320 || p.Cin % 32 || (p.K - 9 * p.Cin) % 32) return false;
   if (gn && (p.upsample || p.Wd != 64 || (p.H * p.Wd) % 256 || p.Cin > 1280)) return false;
   const auto take = [&](int tile, int mode) { *pl = halo_plan(tile, mode, p, ws, ws_floats); return true; };
   if (p.upsample) {  // output width 2 W, output rows per image 2 H
@@ -1548,11 +1537,11 @@ bool plan_halo(const GemmParams& p, bool ws, long ws_floats, bool gn, Plan* pl) 
     if (p.Wd == 32 && ohw % 256 == 0) return take(T256x320, MODE_CONVHUP64);
     if (p.Wd == 8 && ohw % 128 == 0) return take(T128x320, MODE_CONVHUP16);  // 125.6 vs 137.0
     // one prompt per call (<= 32 tiles of 256 output rows): 128-row tiles, 68.8 vs 72.5 us at 2 images
-    if (g_halo == 1 && p.Wd == 16 && ohw % 128 == 0 && (p.M / 256) * (p.N / 320) <= 32)
+    if (halo == 1 && p.Wd == 16 && ohw % 128 == 0 && (p.M / 256) * (p.N / 320) <= 32)
       return take(T128x320, MODE_CONVHUP32);
     // 16 -> 32 upsample on 256-row tiles (8 output rows, K split over slices): 360.3 vs 383.1-395.8 us
-    if (g_halo != 2 && p.Wd == 16 && ohw % 256 == 0) return take(T256x320, MODE_CONVHUP32);
-    if (g_halo < 2) return false;
+    if (halo != 2 && p.Wd == 16 && ohw % 256 == 0) return take(T256x320, MODE_CONVHUP32);
+    if (halo < 2) return false;
     if (p.Wd == 16 && ohw % 128 == 0) return take(T128x320, MODE_CONVHUP32);  // 449 vs 383 us
     return false;
   }
@@ -1560,7 +1549,7 @@ bool plan_halo(const GemmParams& p, bool ws, long ws_floats, bool gn, Plan* pl) 
   // 64-wide outputs at one prompt (<= 32 tiles of 256 rows): 128-row tiles (two output rows), twice the workgroups
   // for the split to fill the chip with: 33.6 vs 41.0 us (320 -> 320) and 43.5 vs 51.1 (640 -> 320) at 2 images,
   // --batch 1 +0.8 % (profiles/r05_halo64_b1.txt)
-  if (g_halo == 1 && p.Wd == 64 && hw % 128 == 0 && (p.M / 256) * (p.N / 320) <= 32)
+  if (halo == 1 && p.Wd == 64 && hw % 128 == 0 && (p.M / 256) * (p.N / 320) <= 32)
     return take(T128x320, MODE_CONVH64);
   if (p.Wd == 64 && hw % 256 == 0) return take(T256x320, MODE_CONVH64);
   // one prompt per call (<= 32 tiles of 256 rows): 128-row tiles for the 16-wide and the narrow-input 32-wide convs,
@@ -1568,44 +1557,41 @@ bool plan_halo(const GemmParams& p, bool ws, long ws_floats, bool gn, Plan* pl) 
   // vs 41.3 (960 -> 640) at 2 images; the Cin >= 1280 32-wide convs keep 256-row tiles (57.8 vs 52.0 us)
   // (profiles/r05_halo128_b1.txt)
   const bool small = (p.M / 256) * (p.N / 320) <= 32;
-  if (g_halo == 1 && small && p.Wd == 16 && hw % 128 == 0) return take(T128x320, MODE_CONVH16);
-  if (g_halo == 1 && small && p.Wd == 32 && hw % 128 == 0 && p.Cin < 1280) return take(T128x320, MODE_CONVH32);
+  if (halo == 1 && small && p.Wd == 16 && hw % 128 == 0) return take(T128x320, MODE_CONVH16);
+  if (halo == 1 && small && p.Wd == 32 && hw % 128 == 0 && p.Cin < 1280) return take(T128x320, MODE_CONVH32);
   // 16-wide outputs: a whole 16x16 image per 256-row tile, K split over slices (1280 -> 1280: 127.6 vs 133.0 us)
-  if (g_halo != 2 && p.Wd == 16 && hw % 256 == 0) return take(T256x320, MODE_CONVH16);
+  if (halo != 2 && p.Wd == 16 && hw % 256 == 0) return take(T256x320, MODE_CONVH16);
   // 32-wide outputs: halo tiles (8 output rows) for the wide-input convs only (up-block conv1, Cin 1920 / 1280): 292 vs
   // 307 us and 206 vs 208 at 16 images, 62 vs 66 and 52 vs 54 at 2; at Cin 640 / 960 they ran 10-14 % slower
   // (profiles/r05_halo32_geglu_diag.txt)
-  if (g_halo == 1 && p.Wd == 32 && hw % 256 == 0 && p.Cin >= 1280) return take(T256x320, MODE_CONVH32);
-  if (g_halo == 3 && p.Wd == 32 && hw % 256 == 0) return take(T256x320, MODE_CONVH32);
-  if (g_halo < 2) return false;
+  if (halo == 1 && p.Wd == 32 && hw % 256 == 0 && p.Cin >= 1280) return take(T256x320, MODE_CONVH32);
+  if (halo == 3 && p.Wd == 32 && hw % 256 == 0) return take(T256x320, MODE_CONVH32);
+  if (halo < 2) return false;
   if (p.Wd == 32 && hw % 128 == 0) return take(T128x320, MODE_CONVH32);
   if (p.Wd == 16 && hw % 128 == 0) return take(T128x320, MODE_CONVH16);
   return false;
 }
 
-// knob 20: 1 (default) = the table-GELU GEGLU on the 256x320 2x4-wave tiles like the ReLU one (no scratch since the
-// [v 2 | g 2] layout: 150.9-154.3 vs 178.2-186.2 us at M = 16384, C = 640; SDXL pipeline +4.0 %, same box);
-// 0 = 256x160 4x2 tiles (rounds 3-4 until the layout change: 364 B/lane of scratch on 256x320)
-int g_gt320 = 1;
-int g_narrow = 1;  // knob 21: 1 (default) = N <= 32 conv outputs (conv_out's 8 padded channels) on 128x32 tiles
-                   // (31.9 vs 34.8-35.1 us at 64x64 x 320 -> 8, same box), 0 = 128x64
-
-// routed-GEGLU linear (MODE_GEGLU / GEGLU_LN / GEGLU_GT): BN in {160, 320} tiles only, no split-K
+// routed-GEGLU linear (MODE_GEGLU / GEGLU_LN / GEGLU_GT): BN in {160, 320} tiles only, no split-K. KNOB_GT320 defaults
+// to the table-GELU GEGLU on the 256x320 2x4-wave tiles like the ReLU one (no scratch since the [v 2 | g 2] layout:
+// 150.9-154.3 vs 178.2-186.2 us at M = 16384, C = 640; SDXL pipeline +4.0 %, same box); its 256x160 4x2 tiles were
+// rounds 3-4's until the layout change (364 B/lane of scratch on 256x320)
 Plan plan_geglu(int mode, const GemmParams& p) {
   const int nt320 = ((p.M + 255) / 256) * (p.N / 320);
   const int nt160_128 = ((p.M + 127) / 128) * (p.N / 160);
   const auto on = [&](int tile) { return tile_plan(mode, tile, p, 1, 0); };
-  if (g_tile == 1) return on(T128x160);
-  if (g_tile == 4) return on(T256x160_42);
-  if (mode != MODE_GEGLU_GT && g_tile == 7) return on(T128x160_42);  // sweep: two workgroups per CU
-  if (mode == MODE_GEGLU_GT && g_tile == 0 && !g_gt320 && p.N % 320 == 0 && nt320 >= 240)
-    // knob 20 = 0: the same rows on 256x160 tiles, 8 waves 4 x 2 (wave tile 64 x 80)
+  const int forced = knob(KNOB_TILE);
+  if (forced == 1) return on(T128x160);
+  if (forced == 4) return on(T256x160_42);
+  if (mode != MODE_GEGLU_GT && forced == 7) return on(T128x160_42);  // sweep: two workgroups per CU
+  if (mode == MODE_GEGLU_GT && forced == 0 && !knob(KNOB_GT320) && p.N % 320 == 0 && nt320 >= 240)
+    // the same rows on 256x160 tiles, 8 waves 4 x 2 (wave tile 64 x 80)
     return on(T256x160_42);
   if (p.N % 320 == 0 && nt320 >= 240) {
     // 2x4 waves (wave tile 128 rows x 40 neurons): with the row-fastest epilogue its 32-row staging passes are
     // conflict-free (4x2's 16-row passes are not: two 16-lane b128 groups mix column pairs); 174.6 vs 181.2 us at
     // M = 65536, 129.8 vs 132.9 at 16384, 103.4 vs 106.4 at 4096 (same box)
-    return on(g_tile == 5 ? T256x320_42 : T256x320);
+    return on(forced == 5 ? T256x320_42 : T256x320);
   }
   // one prompt per call at the 16x16 level (M = 512, N = 10240): 8-wave 128x160 tiles, 20.5 vs 27.3 us on the 4-wave
   // ones (the 32x32 level's M = 2048 measured 24.3 vs 19.0 with them; profiles/r05_b1_geglu_keep_tiles.txt)
@@ -1617,16 +1603,16 @@ Plan plan_geglu(int mode, const GemmParams& p) {
 // Tile rule of the dense modes (GEMM, CONV, CONV_UP, GEMM_LN); the masked modes plan as MODE_GEMM (plan_launch).
 TileRule choose_tile(int mode, const GemmParams& p) {
   const int tm256 = (p.M + 255) / 256;
-  // forced tile (sdmoe_tune knob 1): 1 = 128x160, 2 = 64x160, 3 = 256x320 (8 waves), 4 = 256x160 (8 waves)
-  if (g_tile == 1) return {T128x160, 0, 0};
-  if (g_tile == 2) return {T64x160, 0, 0};
-  if (g_tile == 3 && p.N % 320 == 0) return {T256x320, 0, 0};
-  if (g_tile == 4 && p.N % 160 == 0) return {T256x160_42, 0, 0};
-  if (g_tile == 5 && p.N % 320 == 0) return {T256x320_42, 0, 0};
-  if (g_tile == 6 && p.N % 320 == 0) return {T128x320, 0, 0};
+  const int forced = knob(KNOB_TILE);
+  if (forced == 1) return {T128x160, 0, 0};
+  if (forced == 2) return {T64x160, 0, 0};
+  if (forced == 3 && p.N % 320 == 0) return {T256x320, 0, 0};
+  if (forced == 4 && p.N % 160 == 0) return {T256x160_42, 0, 0};
+  if (forced == 5 && p.N % 320 == 0) return {T256x320_42, 0, 0};
+  if (forced == 6 && p.N % 320 == 0) return {T128x320, 0, 0};
   // sweep-only 8-wave tiles with a 32x80 wave tile (two workgroups per CU on a 2-stage ring)
-  if (mode != MODE_CONV_UP && g_tile == 7 && p.N % 160 == 0) return {T128x160_42, 0, 0};
-  if (mode != MODE_CONV_UP && g_tile == 8 && p.N % 320 == 0) return {T64x320, 0, 0};
+  if (mode != MODE_CONV_UP && forced == 7 && p.N % 160 == 0) return {T128x160_42, 0, 0};
+  if (mode != MODE_CONV_UP && forced == 8 && p.N % 320 == 0) return {T64x320, 0, 0};
   // 8-wave 256x320 tile (wave tile 128x80: 2.5x the MFMA work per LDS byte of 64x80) whenever it alone fills
   // the chip; 256x160 8-wave + split-K for long-K problems whose 128x160 grid is under ~1.2 waves of CUs.
   // Measured on MI355X with tools/gemm_bench.py --tile.
@@ -1677,8 +1663,9 @@ TileRule choose_tile(int mode, const GemmParams& p) {
   if (p.N % 160 == 0 && p.K >= 2560 && nt160_128 < 300 && !(mode == MODE_CONV && p.stride == 2))
     return {T256x160_42, 0, 0};
   if (mode == MODE_CONV_UP) return {p.N % 160 == 0 ? T128x160 : T128x128, 0, 0};
-  // conv_out (N = 8 padded channels): a quarter of 128x64's MFMA padding
-  if (mode == MODE_CONV && p.N <= 32 && g_narrow) return {T128x32, 0, 0};
+  // conv_out (N = 8 padded channels): a quarter of 128x64's MFMA padding (31.9 vs 34.8-35.1 us at 64x64 x 320 -> 8,
+  // same box)
+  if (mode == MODE_CONV && p.N <= 32 && knob(KNOB_NARROW)) return {T128x32, 0, 0};
   if (p.N <= 64) return {T128x64, 0, 0};
   if (p.N % 160 == 0) {
     // plain GEMMs under ~one wave of 128x160 tiles take 64x160 at any M: the 64x64 level's K = 320 projections at one
@@ -1745,8 +1732,12 @@ int launch(const Plan& pl, GemmParams p, float* ws, hipStream_t s) {
   if (pl.ksplit > 1 && !ws) return SDMOE_EARG;
   p.ksplit = pl.ksplit; p.kchunk = pl.kchunk; p.kchunk2 = pl.kchunk2; p.mfast = pl.mfast;
   p.part = pl.ksplit > 1 ? ws : nullptr;
-  p.diag = g_diag; p.res16 = g_res16;
-  p.epi_direct = g_epi_direct == 2 || (g_epi_direct == 1 && p.R == nullptr);  // host-side: a device test of R spilled
+  p.diag = knob(KNOB_DIAG); p.res16 = knob(KNOB_RES16);
+  // fp16 epilogues storing 16-B row pieces straight from the fragments, by default only without a residual: LN-folded
+  // projections 4-12 %, plain K = 320 linears ~3 % faster; with a residual its 16-B residual loads measured 3-7 %
+  // slower than the staged copy-out. Decided host-side: a device test of R spilled
+  const int direct = knob(KNOB_EPI_DIRECT);
+  p.epi_direct = direct == 2 || (direct == 1 && p.R == nullptr);
   const dim3 grid(((p.M + t.bm - 1) / t.bm) * ((p.N + t.bn - 1) / t.bn) * pl.ksplit);
   if (const int st = kLaunch[pl.mode * NTILE + pl.tile](pl, p, grid, s)) return st;
   SDMOE_CHECK_LAUNCH();
@@ -2191,25 +2182,4 @@ extern "C" int sdmoe_mask_weight(const void* W, const void* bits, long N, long K
                                                                    (half_t*)Wm, n8);
   SDMOE_CHECK_LAUNCH();
   return SDMOE_OK;
-}
-
-int sdmoe_attn_set_nqf(int v);  // attention.hip
-int sdmoe_gn_set_fused(int v);  // norm.hip
-extern int g_topk_tpw;          // moe.hip
-
-extern "C" int sdmoe_tune(int knob, int value) {
-  if (knob == 4) return sdmoe_attn_set_nqf(value);
-  if (knob == 7) return sdmoe_gn_set_fused(value);
-  if (knob == 0 && (value == 0 || value == 2 || value == 3)) { g_stages = value; return SDMOE_OK; }
-  if (knob == 1 && value >= 0 && value <= 8) { g_tile = value; return SDMOE_OK; }
-  if (knob == 9 && value >= 0 && value <= 32) { g_ksplit = value; return SDMOE_OK; }
-  if (knob == 14 && (value == 0 || value == 1)) { g_mfast = value; return SDMOE_OK; }
-  if (knob == 6 && value >= 0 && value <= 63) { g_diag = value; return SDMOE_OK; }
-  if (knob == 8 && (value == 0 || value == 1)) { g_res16 = value; return SDMOE_OK; }
-  if (knob == 15 && (value == 0 || value == 1 || value == 4)) { g_topk_tpw = value; return SDMOE_OK; }
-  if (knob == 16 && value >= 0 && value <= 3) { g_halo = value; return SDMOE_OK; }
-  if (knob == 20 && (value == 0 || value == 1)) { g_gt320 = value; return SDMOE_OK; }
-  if (knob == 21 && (value == 0 || value == 1)) { g_narrow = value; return SDMOE_OK; }
-  if (knob == 23 && value >= 0 && value <= 2) { g_epi_direct = value; return SDMOE_OK; }
-  return SDMOE_EARG;
 }

@@ -13,6 +13,7 @@
 // One wave per token, no [tokens, k, 4C] temporaries (reference K5), no host sync (reference K8 is an optional
 // gate_out capture written on device).
 #include "common.h"
+#include "tune.h"
 #include "../../include/sdmoe.h"
 
 namespace {
@@ -489,15 +490,13 @@ __global__ __launch_bounds__(256) void moe_topk_keep_group_kernel(
 
 }  // namespace
 
-int g_topk_tpw = 0;  // sdmoe_tune knob 15: 0 = by M (default; keep bits at E <= 64: one quad per token), 1 / 4 =
-                     // always the ballot kernel at 1 / 4 tokens per wave
-
+// tokens per wave by M, or as KNOB_TOPK forces (1 / 4; include/sdmoe.h)
 template <bool KEEPOUT>
 int launch_topk(half_t* P, long ldp, int M, int F, int E, int esize, int k, const half_t* sc, long ld_score,
                 const uint32_t* rm, uint32_t* sel_out, unsigned long long* keep, hipStream_t s) {
   const int blocks = (M + 15) / 16;  // 16 tokens per workgroup: 4 waves x 4 tokens, or 16 waves x 1 (M <= 16384)
   const size_t lds = KEEPOUT ? (size_t)16 * ((F >> 6) + 1) * 8 : 0;
-  const bool one = g_topk_tpw == 1 || (M <= 16384 && g_topk_tpw != 4);
+  const bool one = knob(KNOB_TOPK) == 1 || (M <= 16384 && knob(KNOB_TOPK) != 4);
 #define SDMOE_TOPK_MASK(SL, SC)                                                                                 \
   if (one)                                                                                                      \
     moe_topk_mask_kernel<SL, SC, KEEPOUT, 1><<<blocks, 1024, lds, s>>>(P, ldp, M, F, E, esize, k, sc, ld_score, \
@@ -537,7 +536,7 @@ extern "C" int sdmoe_moe_topk_keep(int M, int F, int E, int esize, int k, const 
   if (F % 64 || E * esize != F || ld_score < E) return SDMOE_ESHAPE;
   if (E > 256 || esize > 40) return SDMOE_EUNSUP;
   if (k < 0 || k > E) return SDMOE_EARG;
-  if (E <= 64 && g_topk_tpw == 0) {
+  if (E <= 64 && knob(KNOB_TOPK) == 0) {
     const bool full = E == 64 && esize == 20 && ld_score % 8 == 0 && ((uintptr_t)score & 15) == 0;
     hipStream_t s = (hipStream_t)stream;
     const int g = (M + 63) / 64;
@@ -553,7 +552,8 @@ extern "C" int sdmoe_moe_topk_keep(int M, int F, int E, int esize, int k, const 
     SDMOE_CHECK_LAUNCH();
     return SDMOE_OK;
   }
-  if ((E == 128 || E == 256) && esize == 20 && g_topk_tpw == 0 && ld_score % 8 == 0 && ((uintptr_t)score & 15) == 0) {
+  if ((E == 128 || E == 256) && esize == 20 && knob(KNOB_TOPK) == 0 && ld_score % 8 == 0 &&
+      ((uintptr_t)score & 15) == 0) {
     hipStream_t s = (hipStream_t)stream;
     const half_t* sc = (const half_t*)score;
     const uint32_t* rm = (const uint32_t*)removed_bits;

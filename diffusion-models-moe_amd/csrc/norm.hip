@@ -7,13 +7,14 @@
 //   (GroupNorm(32, C, eps=1e-6)), conv_norm_out.
 // LayerNorm (BasicTransformerBlock norm1/2/3, eps=1e-5) is one wave per token row, two-pass in registers.
 #include "common.h"
+#include "tune.h"
 #include "../../include/sdmoe.h"
 
 namespace {
 
 constexpr int GN_SMALL_HW = 1024;  // latents up to 32x32 take the single-launch path (measured crossover)
-int g_gn_fused = 1;  // sdmoe_tune knob 7, sdmoe_groupnorm at HW <= GN_FUSED_HW: 1 = gn_fused_reg_kernel (rows held in
-                     // registers), 2 = gn_fused_kernel (rows re-read for the apply), 0 = two launches
+// KNOB_GN_FUSED picks sdmoe_groupnorm's path at HW <= GN_FUSED_HW: gn_fused_reg_kernel (1), gn_fused_kernel (2) or the
+// two launches (0);
 // single-launch statistics + apply up to 16x16 latents: 13.0 vs 15.9 us at 8x8 (C = 1280, 16 images), 14.5 vs 16.0
 // at 16x16; at 32x32 it is slower (21.9 vs 21.1 us, C = 640; 47.6 vs 42.2 at C = 1920): every block re-reads its
 // chunk's 1024 rows with 16 KB in flight, which no longer hides behind the saved launch (tools/micro_ab.py gn)
@@ -481,12 +482,6 @@ int groupnorm_impl(const void* X, long ldx, int nimg, int HW, int C, int groups,
 }
 }  // namespace
 
-int sdmoe_gn_set_fused(int v) {
-  if (v < 0 || v > 2) return SDMOE_EARG;
-  g_gn_fused = v;
-  return SDMOE_OK;
-}
-
 extern "C" int sdmoe_groupnorm_stats(const void* X, long ldx, int nimg, int HW, int C, int groups,
                                      const void* gamma, const void* beta, float eps, float* scale, float* shift,
                                      float* workspace, long workspace_floats, void* stream) {
@@ -500,7 +495,7 @@ extern "C" int sdmoe_groupnorm(const void* X, long ldx, int nimg, int HW, int C,
   if (!Y || ldy % 8) return Y ? SDMOE_ESHAPE : SDMOE_EARG;
   // small latents: statistics + apply in one launch, the rows of each chunk split over S slices so the grid keeps
   // >= ~512 blocks (one block per chunk -- 128-256 blocks -- streamed the output 0.4-1 % slower end to end)
-  if (g_gn_fused && HW <= GN_FUSED_HW && X && gamma && beta && nimg > 0 && groups > 0 && C % groups == 0 &&
+  if (knob(KNOB_GN_FUSED) && HW <= GN_FUSED_HW && X && gamma && beta && nimg > 0 && groups > 0 && C % groups == 0 &&
       C % 8 == 0 && ldx % 8 == 0 && groups <= 64) {
     const int wc = gn_chunk_width(C, groups);
     if (wc) {
@@ -513,7 +508,7 @@ extern "C" int sdmoe_groupnorm(const void* X, long ldx, int nimg, int HW, int C,
       hipStream_t st = (hipStream_t)stream;
       const half_t *x = (const half_t*)X, *g = (const half_t*)gamma, *b = (const half_t*)beta;
       const int rpt = (HW + R - 1) / R;  // rows per thread of the register-resident kernel
-      if (g_gn_fused == 1 && rpt <= 16) {
+      if (knob(KNOB_GN_FUSED) == 1 && rpt <= 16) {
         if (rpt <= 4) gn_fused_reg_kernel<4><<<grid, 256, 0, st>>>(x, ldx, HW, C, groups, wc, S, g, b, eps, silu, (half_t*)Y, ldy, scale, shift);
         else if (rpt <= 8) gn_fused_reg_kernel<8><<<grid, 256, 0, st>>>(x, ldx, HW, C, groups, wc, S, g, b, eps, silu, (half_t*)Y, ldy, scale, shift);
         else gn_fused_reg_kernel<16><<<grid, 256, 0, st>>>(x, ldx, HW, C, groups, wc, S, g, b, eps, silu, (half_t*)Y, ldy, scale, shift);

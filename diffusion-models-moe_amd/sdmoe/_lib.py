@@ -16,6 +16,7 @@ _L = ctypes.c_long
 _I = ctypes.c_int
 _F = ctypes.c_float
 _FP = ctypes.POINTER(ctypes.c_float)
+_IP = ctypes.POINTER(ctypes.c_int)
 
 # name -> argtypes, in the exact order of include/sdmoe.h
 SIGNATURES = {
@@ -61,6 +62,8 @@ SIGNATURES = {
     "sdmoe_cfg_ddim_step": [_P, _L, _P, _I, _I, _I, _F, _F, _F, _P, _L, _P],
     "sdmoe_add": [_P, _P, _P, _L, _P],
     "sdmoe_tune": [_I, _I],
+    "sdmoe_tune_knob": [_I, _IP, ctypes.POINTER(ctypes.c_char_p), _IP, _IP],
+    "sdmoe_tune_reset": [],
     "sdmoe_set_gelu_table": [_P],
     "sdmoe_version": [],
 }
@@ -96,23 +99,45 @@ def load(path: str | None = None):
         fn.argtypes = argt
         fn.restype = ctypes.c_char_p if name == "sdmoe_version" else ctypes.c_int
     # A/B experiments without code changes: SDMOE_TUNE="knob=value,..." (sdmoe_tune, include/sdmoe.h)
-    for k, v in parse_tune(os.environ.get("SDMOE_TUNE", "")):
+    for k, v in parse_tune(os.environ.get("SDMOE_TUNE", ""), lib):
         check(lib.sdmoe_tune(k, v), f"sdmoe_tune({k}={v})")
     _lib = lib
     return lib
 
 
-def parse_tune(spec: str):
-    """SDMOE_TUNE="knob=value,..." -> [(knob, value)]; malformed entries raise SdmoeError (not a bare ValueError)."""
+def knob_table(lib=None):
+    """The library's knob table (sdmoe_tune_knob): [(id, name, default, value)]. An SDMOE_AB=1 library from before the
+    table raises: no copy of it is kept here."""
+    lib = lib or load()
+    if not has(lib, "sdmoe_tune_knob"):
+        raise SdmoeError("this library has no sdmoe_tune_knob (an older SDMOE_AB=1 build): its knobs can be set by id "
+                         "through sdmoe_tune / SDMOE_TUNE only, not named, read or restored")
+    rows = []
+    kid, dflt, val, name = _I(), _I(), _I(), ctypes.c_char_p()
+    while lib.sdmoe_tune_knob(len(rows), kid, name, dflt, val) == 0:
+        rows.append((kid.value, name.value.decode(), dflt.value, val.value))
+    return rows
+
+
+def parse_tune(spec: str, lib=None):
+    """SDMOE_TUNE="knob=value,..." -> [(id, value)], knob an id or a name of the library's table (`lib`: the library to
+    look names up in, default load()); malformed entries raise SdmoeError (not a bare ValueError)."""
     out = []
     for kv in filter(None, (s.strip() for s in spec.split(","))):
-        parts = kv.split("=")
+        parts = [s.strip() for s in kv.split("=")]
         if len(parts) != 2:
             raise SdmoeError(f"SDMOE_TUNE entry {kv!r}: expected knob=value")
         try:
-            out.append((int(parts[0]), int(parts[1])))
+            value = int(parts[1])
+            knob = int(parts[0]) if not parts[0].isidentifier() else None
         except ValueError:
-            raise SdmoeError(f"SDMOE_TUNE entry {kv!r}: knob and value must be integers") from None
+            raise SdmoeError(f"SDMOE_TUNE entry {kv!r}: knob must be an id or a name, value an integer") from None
+        if knob is None:
+            ids = {name: kid for kid, name, _, _ in knob_table(lib)}
+            if parts[0] not in ids:
+                raise SdmoeError(f"SDMOE_TUNE entry {kv!r}: no knob named {parts[0]!r} (known: {', '.join(ids)})")
+            knob = ids[parts[0]]
+        out.append((knob, value))
     return out
 
 

@@ -369,29 +369,52 @@ int sdmoe_cfg_multistep_step(const void* eps, long lde, float* lat, int B, int H
                              float* hist, float* cur, const float* coef, const int* flags, void* next_in, long ldn,
                              void* stream);
 
-/* Tuning knobs for A/B experiments: knob 0 = GEMM LDS pipeline stages (0 auto, 2 or 3); knob 1 = forced GEMM tile
-   (0 auto, 1 = 128x160, 2 = 64x160, 3 = 256x320 8-wave, 4 = 256x160 8-wave, 5 = 256x320 4x2-wave, 6 = 128x320 8-wave,
-   7 = 128x160 8-wave, 8 = 64x320 8-wave; 7/8 plain GEMM / conv / LN-folded GEMM only); knob 9 = forced split-K
-   factor (0 auto, 1 = never split, 2..32; halo convs: at most one 32-channel slice per split); knob 14 = split-K conv tile order: 1 (default) M-tile fastest (one XCD's
-   workgroups share weight slices in its L2), 0 split fastest; knob 4 = attention kernel (0 auto by shape,
-   1 = 32x32x16 MFMA kernel, 2 / 4 = 4-wave 16x16x32 kernel with 32 / 64 queries per wave, 64 for head_dim <= 40
-   only; 8 = 16x16x32 kernel in 8-wave workgroups (head_dim <= 80));
-   knob 6 = GEMM diagnostics bits (1 no K-loop loads, 2 no MFMA, 4 no epilogue, 8 no global stores);
-   knob 7 = sdmoe_groupnorm at HW <= 256: 1 (default) statistics + apply in one launch with the rows held in
-   registers, 2 the same launch re-reading the rows for the apply, 0 two launches;
-   knob 8 = GEMM residual epilogue: 1 (default) output rounded to fp16 then the residual added in fp16 arithmetic
-   (diffusers' fp16 `linear(x) + residual`), 0 = accumulator + residual rounded once (fp32 staging);
-   knob 15 = top-k expert selection kernels: 0 (default) one token per wave at M <= 16384, four above, and the keep
-   bits at E <= 64 with one quad of lanes per token; 1 / 4 = always the ballot kernel at one / four tokens per wave;
-   knob 16 = halo-tiled 3x3 convs: 1 (default) where measured faster (64- and 16-wide outputs, the upsample convs,
-   32-wide outputs with Cin >= 1280; grids of <= 32 256-row tiles -- one prompt per call -- on 128-row tiles for the
-   64-, 16- and narrow-input 32-wide outputs and the 16 -> 32 upsample), 2 = every 128-row halo tile instead, 3 = the
-   default plus every 32-wide output on 256-row tiles, 0 = off;
-   knob 20 = table-GELU routed GEGLU tiles: 1 (default) 256x320 like the ReLU kernel, 0 = 256x160 (4x2 waves);
-   knob 21 = convs with at most 32 output channels (conv_out): 1 (default) 128x32 tiles, 0 = 128x64;
-   knob 23 = fp16 GEMM / conv epilogues: 1 (default) 16-B row pieces stored straight from the MFMA fragments (two
-   v_permlane16_swap per fragment pair, no LDS staging) when there is no residual, 2 = always, 0 = staged in LDS. */
+/*
+ * Tuning knobs for A/B experiments: process-wide integers the launch code reads. Ids, legal values and defaults are
+ * ABI (recorded command lines name them). This is the one definition of what each value means; the library's table
+ * (csrc/tune.hip) holds id, name, default and legal set. sdmoe_tune returns -1 for an unknown knob or an illegal
+ * value and then leaves the knob unchanged. Not synchronised: set knobs between launches, from one thread.
+ *   0 stages      GEMM LDS ring depth: 0 (default) auto, 2 or 3;
+ *   1 tile        forced GEMM tile: 0 (default) auto, 1 = 128x160, 2 = 64x160, 3 = 256x320 8-wave, 4 = 256x160 8-wave,
+ *                 5 = 256x320 4x2-wave, 6 = 128x320 8-wave, 7 = 128x160 8-wave, 8 = 64x320 8-wave (7 / 8: plain GEMM /
+ *                 conv / LN-folded GEMM only); a forced tile also turns the halo convs off;
+ *   4 attn        attention kernel: 0 (default) by shape, 1 = 32x32x16 MFMA kernel, 2 / 4 = 4-wave 16x16x32 kernel with
+ *                 32 / 64 queries per wave (64 for head_dim <= 40 only), 8 = 16x16x32 kernel in 8-wave workgroups,
+ *                 9 = 32x32x16 kernel in 8-wave workgroups (8 / 9: head_dim <= 80);
+ *   6 diag        GEMM diagnostics bits, results garbage, 0..63 (default 0): 1 no K-loop operand loads, 2 no MFMAs,
+ *                 4 no epilogue (nothing stored), 8 epilogue without its global stores, 16 no A-operand pieces,
+ *                 32 no B-operand pieces;
+ *   7 gn_fused    sdmoe_groupnorm at HW <= 256: 1 (default) statistics + apply in one launch with the rows held in
+ *                 registers, 2 the same launch re-reading the rows for the apply, 0 two launches;
+ *   8 res16       GEMM residual epilogue: 1 (default) output rounded to fp16 then the residual added in fp16 arithmetic
+ *                 (diffusers' fp16 `linear(x) + residual`), 0 = accumulator + residual rounded once (fp32 staging);
+ *   9 ksplit      forced split-K factor: 0 (default) auto, 1 = never split, 2..32 (clamped to the K-steps; halo convs:
+ *                 at most one 32-channel slice per split);
+ *  14 mfast       split-K conv tile order: 1 (default) M-tile fastest (one XCD's workgroups share weight slices in its
+ *                 L2), 0 split fastest;
+ *  15 topk        top-k expert selection kernels: 0 (default) one token per wave at M <= 16384, four above, and the
+ *                 keep bits at E <= 64 with one quad of lanes per token; 1 / 4 = always the ballot kernel at one /
+ *                 four tokens per wave;
+ *  16 halo        halo-tiled 3x3 convs: 1 (default) where measured faster (64- and 16-wide outputs, the upsample convs,
+ *                 32-wide outputs with Cin >= 1280; grids of <= 32 256-row tiles -- one prompt per call -- on 128-row
+ *                 tiles for the 64-, 16- and narrow-input 32-wide outputs and the 16 -> 32 upsample), 2 = every 128-row
+ *                 halo tile instead, 3 = the default plus every 32-wide output on 256-row tiles, 0 = off;
+ *  20 gt320       table-GELU routed GEGLU tiles: 1 (default) 256x320 like the ReLU kernel, 0 = 256x160 (4x2 waves);
+ *  21 narrow      convs with at most 32 output channels (conv_out): 1 (default) 128x32 tiles, 0 = 128x64;
+ *  23 epi_direct  fp16 GEMM / conv epilogues: 1 (default) 16-B row pieces stored straight from the MFMA fragments (two
+ *                 v_permlane16_swap per fragment pair, no LDS staging) when there is no residual, 2 = always,
+ *                 0 = staged in LDS.
+ */
 int sdmoe_tune(int knob, int value);
+
+/*
+ * Enumerates the knob table: entry `index` (0 .. until it returns -1) gives the knob's id, its short name (a static
+ * string), its default and its current value. -1 for an index past the end or a null output pointer. Host only.
+ */
+int sdmoe_tune_knob(int index, int* id, const char** name, int* default_value, int* value);
+
+/* Sets every knob to its default. Host only. */
+int sdmoe_tune_reset(void);
 
 /*
  * Registers, for the calling thread's current HIP device, the fp16 GELU table the GEGLU kernels apply for

@@ -12,7 +12,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from sdmoe import ops  # noqa: E402
+from sdmoe import ops, tune  # noqa: E402
 
 DEV = "cuda"
 TOL = 1e-2
@@ -142,10 +142,7 @@ def test_conv3x3_strided_concat_input():
 @pytest.mark.parametrize("tile", [1, 2, 3, 4, 5, 6, 7, 8])
 def test_forced_tiles(tile):
     """Every tile configuration of the GEMM kernel (sdmoe_tune knob 1), in all three modes, with ragged M."""
-    from sdmoe import _lib
-    lib = _lib.load()
-    _lib.check(lib.sdmoe_tune(1, tile), "tune")
-    try:
+    with tune.tuned(tile=tile):
         x = rnd(1000, 640, seed=40)
         w = rnd(1280, 640, scale=640 ** -0.5, seed=41)
         b = rnd(1280, scale=0.1, seed=42)
@@ -155,8 +152,6 @@ def test_forced_tiles(tile):
             wi = rnd(Cout, 3, 3, Cin, scale=(9 * Cin) ** -0.5, seed=44)
             bi = rnd(Cout, scale=0.1, seed=45)
             close(ops.conv3x3(xi, 2, H, H, ops.conv_weight(wi), bi, stride=st, upsample=up), conv_ref(xi, 2, H, H, wi, bi, st, up))
-    finally:
-        _lib.check(lib.sdmoe_tune(1, 0), "tune")
 
 
 @pytest.mark.parametrize("nimg,HW,C,N,mean", [(16, 4096, 320, 320, 0.0), (16, 1024, 640, 640, 0.0), (3, 256, 1280, 1280, 2.0),
@@ -271,18 +266,13 @@ def test_attention_forced_variant(variant, d, Nq, Nk):
     """Every attention kernel variant (sdmoe_tune knob 4: 1 = 32x32x16 kernel, 2 / 4 = 16x16x32 kernel with 32 / 64
     queries per wave, 8 = 16x16x32 kernel in 8-wave workgroups, 9 = 32x32x16 kernel in 8-wave workgroups), ragged Nq
     and Nk, single-tile and exactly-whole-tile key counts."""
-    from sdmoe import _lib
-    lib = _lib.load()
     nimg, heads = 2, 4
     C = heads * d
     q = rnd(nimg * Nq, C, seed=60)
     kv = rnd(nimg * Nk, 2 * C, seed=61)
     k, v = kv[:, :C], kv[:, C:]
-    _lib.check(lib.sdmoe_tune(4, variant), "tune")
-    try:
+    with tune.tuned(attn=variant):
         out = ops.attention(q, k, v, nimg, Nq, Nk, heads)
-    finally:
-        _lib.check(lib.sdmoe_tune(4, 0), "tune")
     qf = q.float().reshape(nimg, Nq, heads, d).transpose(1, 2)
     kf = k.float().reshape(nimg, Nk, heads, d).transpose(1, 2)
     vf = v.float().reshape(nimg, Nk, heads, d).transpose(1, 2)
@@ -293,19 +283,14 @@ def test_attention_forced_variant(variant, d, Nq, Nk):
 @pytest.mark.parametrize("d,variant", [(80, 0), (40, 0), (40, 8), (40, 9), (40, 1)])
 def test_attention_peaked_softmax(d, variant):
     """A spiked key forces the online-softmax rescale branch at a later tile."""
-    from sdmoe import _lib
-    lib = _lib.load()
     nimg, heads, N = 1, 8, 512
     C = heads * d
     q = rnd(nimg * N, C, seed=42)
     k = rnd(nimg * N, C, seed=43)
     k[300] = q[5] * 4  # query 5 now peaks at key 300 (tile 4)
     v = rnd(nimg * N, C, seed=44)
-    _lib.check(lib.sdmoe_tune(4, variant), "tune")
-    try:
+    with tune.tuned(attn=variant):
         out = ops.attention(q, k, v, nimg, N, N, heads)
-    finally:
-        _lib.check(lib.sdmoe_tune(4, 0), "tune")
     qf = q.float().view(1, N, heads, d).transpose(1, 2)
     kf = k.float().view(1, N, heads, d).transpose(1, 2)
     vf = v.float().view(1, N, heads, d).transpose(1, 2)
@@ -358,22 +343,6 @@ def test_attention_full_size(d, N):
     close(out, ref)
 
 
-def _with_tune(settings, fn):
-    from sdmoe import _lib
-    lib = _lib.load()
-    try:
-        for knob, val in settings:
-            _lib.check(lib.sdmoe_tune(knob, val), "tune")
-        fn()
-    finally:
-        _lib.check(lib.sdmoe_tune(0, 0), "tune")
-        _lib.check(lib.sdmoe_tune(1, 0), "tune")
-        _lib.check(lib.sdmoe_tune(9, 0), "tune")
-        _lib.check(lib.sdmoe_tune(16, 1), "tune")
-        _lib.check(lib.sdmoe_tune(20, 1), "tune")
-        _lib.check(lib.sdmoe_tune(21, 1), "tune")
-
-
 # tiles (sdmoe_tune knob 1): 0 auto, 1 = 128x160, 2 = 64x160, 3 = 256x320 (2x4 waves), 4 = 256x160 (4x2), 5 = 256x320
 # (4x2), 7 = 128x160 (4x2, 8 waves), 8 = 64x320 (2x4, 8 waves); stages (knob 0): 0 auto, 2, 3 -- every ring the
 # M = 65,536 problems can take
@@ -387,9 +356,8 @@ def test_linear_full_size_tiles(tile, stages):
     x, w = rnd(M, K, seed=60), rnd(N, K, scale=K ** -0.5, seed=61)
     b, r = rnd(N, scale=0.1, seed=62), rnd(M, N, seed=63)
 
-    def run():
+    with tune.tuned(tile=tile, stages=stages):
         close(ops.linear(x, w, b, residual=r), x.float() @ w.float().t() + b.float() + r.float())
-    _with_tune([(1, tile), (0, stages)], run)
 
 
 @pytest.mark.parametrize("tile,stages", FULL_TILES)
@@ -401,10 +369,9 @@ def test_conv3x3_full_size_tiles(tile, stages):
     w, b = rnd(C, 3, 3, C, scale=(9 * C) ** -0.5, seed=65), rnd(C, scale=0.1, seed=66)
     temb, res = rnd(1, C, seed=67), rnd(nimg * H * H, C, seed=68)
 
-    def run():
+    with tune.tuned(tile=tile, stages=stages):
         out = ops.conv3x3(x, nimg, H, H, ops.conv_weight(w), b, coladd=temb, coladd_bstride=0, residual=res)
         close(out, conv_ref(x, nimg, H, H, w, b) + temb.float() + res.float())
-    _with_tune([(1, tile), (0, stages)], run)
 
 
 @pytest.mark.parametrize("H,Cin,Cout,nimg,up", [(64, 320, 320, 16, False), (64, 960, 320, 2, False),
@@ -432,7 +399,8 @@ def test_conv3x3_halo_tiles(H, Cin, Cout, nimg, up):
     # 1 default (64-wide at <= 32 tiles: 128-row tiles); 2: the 128-row halo tiles the default leaves off; 3: 32-wide
     # outputs on 256-row tiles; 0: shifted
     for halo in (1, 2, 3, 0):
-        _with_tune([(16, halo)], lambda: outs.append(ops.conv3x3(x, nimg, H, H, wc, b, upsample=up, **kw)))
+        with tune.tuned(halo=halo):
+            outs.append(ops.conv3x3(x, nimg, H, H, wc, b, upsample=up, **kw))
     for o in outs:
         close(o, ref)
     for o in outs[:3]:
@@ -446,9 +414,9 @@ def test_conv3x3_narrow_outputs(Cout, narrow):
     for nimg, H, Cin in [(2, 64, 320), (3, 10, 128)]:
         x = rnd(nimg * H * H, Cin, seed=Cout + H)
         w, b = rnd(Cout, 3, 3, Cin, scale=(9 * Cin) ** -0.5, seed=Cout), rnd(Cout, scale=0.1, seed=Cout + 1)
-        out = []
-        _with_tune([(21, narrow)], lambda: out.append(ops.conv3x3(x, nimg, H, H, ops.conv_weight(w), b)))
-        close(out[0], conv_ref(x, nimg, H, H, w, b))
+        with tune.tuned(narrow=narrow):
+            out = ops.conv3x3(x, nimg, H, H, ops.conv_weight(w), b)
+        close(out, conv_ref(x, nimg, H, H, w, b))
 
 
 @pytest.mark.parametrize("Cin,Cout,Cin2,nimg,res", [(320, 320, 0, 16, True), (960, 320, 0, 2, False), (640, 320, 0, 3, False),
@@ -495,9 +463,9 @@ def test_conv3x3_halo_upsample_forced_splits(H, C, nimg, ks):
     vs torch fp32 (nearest upsample, then the 3x3 conv)."""
     x = rnd(nimg * H * H, C, seed=H + ks)
     w, b = rnd(C, 3, 3, C, scale=(9 * C) ** -0.5, seed=H + 1), rnd(C, scale=0.1, seed=H + 2)
-    out = []
-    _with_tune([(9, ks)], lambda: out.append(ops.conv3x3(x, nimg, H, H, ops.conv_weight(w), b, upsample=True)))
-    close(out[0], conv_ref(x, nimg, H, H, w, b, 1, True))
+    with tune.tuned(ksplit=ks):
+        out = ops.conv3x3(x, nimg, H, H, ops.conv_weight(w), b, upsample=True)
+    close(out, conv_ref(x, nimg, H, H, w, b, 1, True))
 
 
 @pytest.mark.parametrize("Cin,Cin2", [(320, 640), (640, 0)])
@@ -517,13 +485,10 @@ def test_conv3x3_groupnorm_in_kernel_forced_splits(Cin, Cin2, ks):
         kw = dict(shortcut=x2)
     else:
         wc, kw = ops.conv_weight(w), dict(residual=rnd(nimg * H * H, Cout, seed=17))
-    outs = []
-
-    def run():
-        outs.append(ops.conv3x3(x, nimg, H, H, wc, b, gn=(sc, sh, True), **kw))
-        outs.append(ops.conv3x3(ops.groupnorm_apply(x, nimg, H * H, sc, sh, True), nimg, H, H, wc, b, **kw))
-    _with_tune([(9, ks)], run)
-    assert torch.equal(outs[0], outs[1])
+    with tune.tuned(ksplit=ks):
+        fused = ops.conv3x3(x, nimg, H, H, wc, b, gn=(sc, sh, True), **kw)
+        unfused = ops.conv3x3(ops.groupnorm_apply(x, nimg, H * H, sc, sh, True), nimg, H, H, wc, b, **kw)
+    assert torch.equal(fused, unfused)
 
 
 def test_conv3x3_full_size_upsample_concat():
@@ -562,10 +527,8 @@ def test_geglu_fused_full_size(M, C, E, tile):
     routing = ops.Routing(torch.randperm(F_, generator=g) % E, E, 12, DEV)
     w_il, b_il = ops.interleave_geglu(w, b, routing.perm)
     score = torch.empty((M, E), dtype=torch.float16, device=DEV)
-    res = []
-    _with_tune([(1, tile)], lambda: res.append(ops.linear_geglu(x, w_il, b_il, ops.ACT_RELU, score=score,
-                                                                esize=routing.esize)))
-    P = res[0]
+    with tune.tuned(tile=tile):
+        P = ops.linear_geglu(x, w_il, b_il, ops.ACT_RELU, score=score, esize=routing.esize)
     score_u = torch.empty_like(score)
     out_u = ops.geglu_route(ops.linear(x, w, b), routing, ops.ACT_RELU, score_out=score_u, k=E)
     assert torch.equal(score, score_u)
@@ -682,20 +645,15 @@ def test_groupnorm_single_launch_bit_identical(HW, C, nimg, silu):
     gn_fused_kernel, knob 7 = 2) vs the two-launch path (gn_small_kernel + gn_apply_kernel, knob 7 = 0): the same
     sums in the same order, the same fp64 finalize and the same fp32 scale/shift, so the outputs are bit-identical;
     strided input/output views."""
-    from sdmoe import _lib
-    lib = _lib.load()
     buf = rnd(nimg * HW, C + 64, seed=HW + C) * 2 + 1
     x = buf[:, 64:]
     gamma, beta = rnd(C, scale=0.1, seed=C + 1) + 1, rnd(C, scale=0.1, seed=C + 2)
     outs = []
     for mode in (1, 2, 0):
-        _lib.check(lib.sdmoe_tune(7, mode), "tune")
-        try:
+        with tune.tuned(gn_fused=mode):
             dst = torch.full((nimg * HW, C + 16), 7.0, dtype=torch.float16, device=DEV)
             ops.groupnorm(x, nimg, HW, gamma, beta, 1e-5, 32, silu, out=dst[:, 8:8 + C])
             outs.append(dst)
-        finally:
-            _lib.check(lib.sdmoe_tune(7, 1), "tune")
     assert torch.equal(outs[0], outs[2]) and torch.equal(outs[1], outs[2])
     assert (outs[0][:, :8] == 7).all() and (outs[0][:, 8 + C:] == 7).all()
     ref = F.group_norm(x.float().reshape(nimg, HW, C).permute(0, 2, 1), 32, gamma.float(), beta.float(), 1e-5)
@@ -757,11 +715,11 @@ def test_conv3x3_halo_forced_splits(H, C, Cin2, nimg, ks):
     wsc = rnd(C, Cin2, scale=Cin2 ** -0.5, seed=114)
     b = rnd(C, scale=0.1, seed=115)
     wcat = ops.conv_weight_with_shortcut(ops.conv_weight_from_torch(w), wsc)
-    out = []
-    _with_tune([(9, ks)], lambda: out.append(ops.conv3x3(hn, nimg, H, H, wcat, b, shortcut=x)))
+    with tune.tuned(ksplit=ks):
+        out = ops.conv3x3(hn, nimg, H, H, wcat, b, shortcut=x)
     xi = hn.float().reshape(nimg, H, H, C).permute(0, 3, 1, 2)
     ref = F.conv2d(xi, w.float(), b.float(), padding=1).permute(0, 2, 3, 1).reshape(-1, C)
-    close(out[0], ref + x.float() @ wsc.float().t())
+    close(out, ref + x.float() @ wsc.float().t())
 
 
 @pytest.mark.parametrize("kind", ["linear", "linear_res", "linear_ln", "conv_temb", "conv_halo_sc", "keep", "per_image"])
@@ -812,5 +770,6 @@ def test_direct_epilogue_bit_identical(kind):
         return ops.linear_per_image(x, wf, colf, HW)
 
     for mode in (0, 2, 1):
-        _with_tune([(23, mode)], lambda: outs.append(run()))
+        with tune.tuned(epi_direct=mode):
+            outs.append(run())
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])

@@ -24,24 +24,10 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from sdmoe import _lib, ops  # noqa: E402
+from sdmoe.tune import tuned  # noqa: E402
 from test_gpu_kernels import DEV, close, conv_ref, rnd  # noqa: E402
 
-# every knob these tests touch, with its default (include/sdmoe.h, csrc/gemm.hip)
-KNOB_DEFAULTS = {0: 0, 1: 0, 9: 0, 16: 1, 8: 1, 14: 1, 23: 1}
 SENTINEL = 12345.0
-
-
-@contextlib.contextmanager
-def tuned(settings):
-    """Apply sdmoe_tune knobs {knob: value}; restore every knob this file can touch to its default afterwards."""
-    lib = _lib.load()
-    try:
-        for knob, val in settings.items():
-            _lib.check(lib.sdmoe_tune(knob, val), f"sdmoe_tune({knob}, {val})")
-        yield
-    finally:
-        for knob, val in KNOB_DEFAULTS.items():
-            _lib.check(lib.sdmoe_tune(knob, val), f"sdmoe_tune({knob}, {val})")
 
 
 class _Workspace:
@@ -156,7 +142,7 @@ def test_linear_forced_splits(M, N, K, ks):
     ksplit = expected_splits(K // 64, ks)
     if (M, N, K) == (77, 320, 704):
         assert ksplit == {2: 2, 3: 3, 4: 4, 5: 4, 7: 6, 32: 11}[ks]
-    with tuned({9: ks}):
+    with tuned(ksplit=ks):
         out = run_gemm("plain", M, N, K, ksplit, lambda: ops.linear(x, w, b, residual=r), residual=True)
     close(out, x.float() @ w.float().t() + b.float() + r.float())
 
@@ -171,7 +157,7 @@ def test_linear_forced_tiles_under_a_split(tile):
     an M tail in every one of them."""
     M, N, K = 300, 1280, 640
     x, w, b, _ = _linear_operands(M, N, K, 210)
-    with tuned({9: 3, 1: tile}):
+    with tuned(ksplit=3, tile=tile):
         out = run_gemm("plain", M, N, K, 3, lambda: ops.linear(x, w, b), tile=TILES[tile])
     close(out, x.float() @ w.float().t() + b.float())
 
@@ -193,7 +179,7 @@ def test_linear_epilogues_through_the_reduce(epi):
     M, N, K = 77, 320, 704
     x, w, b, r = _linear_operands(M, N, K, 220)
     acc = x.float() @ w.float().t() + b.float()
-    knobs, kw, act, res = {9: 4}, {}, ops.ACT_NONE, False
+    knobs, kw, act, res = {"ksplit": 4}, {}, ops.ACT_NONE, False
     if epi == "bias":
         ref = acc
     elif epi in ACT_FN:
@@ -204,7 +190,7 @@ def test_linear_epilogues_through_the_reduce(epi):
         kw = dict(coladd=col, coladd_bstride=N, rows_per_batch=7)
         ref = acc + col.float().repeat_interleave(7, 0)
     elif epi in ("res16", "res32"):
-        knobs[8] = 1 if epi == "res16" else 0
+        knobs["res16"] = 1 if epi == "res16" else 0
         kw, res, ref = dict(residual=r), True, acc + r.float()
     elif epi == "act_res":
         act, kw, res, ref = ops.ACT_SILU, dict(residual=r), True, F.silu(acc) + r.float()
@@ -215,7 +201,7 @@ def test_linear_epilogues_through_the_reduce(epi):
         x, r = xbig[:, 64:64 + K], rbig[:, 8:8 + N]
         kw, res = dict(residual=r, out=dst[:, 8:8 + N]), True
         ref = x.float() @ w.float().t() + b.float() + r.float()
-    with tuned(knobs):
+    with tuned(**knobs):
         out = run_gemm("plain", M, N, K, 4, lambda: ops.linear(x, w, b, act=act, **kw), residual=res, act=act)
     close(out, ref)
     if epi == "strided":
@@ -228,7 +214,7 @@ def test_linear_fp32_residual_unsplit():
     x, w, b, r = _linear_operands(M, N, K, 230)
     outs = {}
     for res16 in (0, 1):
-        with tuned({9: 1, 8: res16}):
+        with tuned(ksplit=1, res16=res16):
             outs[res16] = run_gemm("plain", M, N, K, 1, lambda: ops.linear(x, w, b, residual=r), residual=True)
         close(outs[res16], x.float() @ w.float().t() + b.float() + r.float())
 
@@ -241,7 +227,7 @@ def test_linear_workspace_lowers_the_split(extra, ksplit):
     M, N, K = 77, 320, 704
     x, w, b, r = _linear_operands(M, N, K, 240)
     floats = {"3mn+4": 3 * M * N + 4, "mn": M * N, "zero": 0}[extra]
-    with tuned({9: 8}):
+    with tuned(ksplit=8):
         assert ops.gemm_plan("plain", M, N, K, residual=True)["ksplit"] == 6  # (with room: 8 wanted -> 2 per split)
         out = run_gemm("plain", M, N, K, ksplit, lambda: ops.linear(x, w, b, residual=r), residual=True, floats=floats)
     close(out, x.float() @ w.float().t() + b.float() + r.float())
@@ -268,7 +254,7 @@ def test_linear_weight_row_stride_above_k(ks, workspace):
                               out.data_ptr(), out.stride(0), M, N, K, ops.ACT_NONE, wsp, wsn, ops._stream())
         _lib.check(st, "sdmoe_linear")
         return out
-    with tuned({9: ks}):
+    with tuned(ksplit=ks):
         if workspace:
             run_gemm("plain", M, N, K, ksplit, call)
         else:
@@ -307,7 +293,7 @@ def test_masked_linear_forced_splits(kind, ks):
     res = kind == "linear_keep"
     bias, rr = (b, r) if res else (None, None)
     xm = x * keep01 if use_keep else x
-    with tuned({9: ks}):
+    with tuned(ksplit=ks):
         wm = ops.mask_weight(w, bits) if use_w else w
         if kind == "linear_keep":
             fn = lambda: ops.linear_keep(x, keep, w, bias, residual=rr)  # noqa: E731
@@ -334,7 +320,7 @@ def test_linear_per_image_forced_splits(res, ks):
     colf = rnd(nimg, N, seed=312).float()
     r = rnd(M, N, seed=313) if res else None
     ksplit = expected_splits(K // 64, ks)
-    with tuned({9: ks}):
+    with tuned(ksplit=ks):
         out = run_gemm("plain", M, N, K, ksplit, lambda: ops.linear_per_image(x, wf, colf, rpb, residual=r), residual=res)
     ref = torch.cat([x[i * rpb:(i + 1) * rpb].float() @ wf[i].float().t() + colf[i] for i in range(nimg)])
     close(out, ref + (r.float() if res else 0))
@@ -401,7 +387,7 @@ def test_shifted_conv_nonsquare_forced_splits(fam, H, W, ks, full):
     act = kw.get("act", ops.ACT_NONE)
     outs = []
     for mfast in (1, 0):
-        with tuned({9: ks, 14: mfast}):
+        with tuned(ksplit=ks, mfast=mfast):
             outs.append(run_conv(nimg, H, W, Cin, Cout, ksplit,
                                  lambda: ops.conv3x3(x, nimg, H, W, wc, b, stride=stride, upsample=up, **kw),
                                  halo=False, Cin2=Cin2, stride=stride, upsample=up, residual="residual" in kw, act=act))
@@ -450,7 +436,7 @@ def _halo_problem(H, W, upsample, Cin2):
         r = rnd(nimg * OH * OW, Cout, seed=seed + 4)
         kw.update(residual=r)
         ref = ref + r.float()
-    with tuned({16: 0, 9: 1}):
+    with tuned(halo=0, ksplit=1):
         shifted = run_conv(nimg, H, W, Cin, Cout, 1, lambda: ops.conv3x3(x, nimg, H, W, wc, b, upsample=upsample, **kw),
                            halo=False, Cin2=Cin2, upsample=upsample, residual=not Cin2)
     close(shifted, ref)
@@ -462,7 +448,7 @@ def _run_halo(H, W, ks, rows, *, knob16=1, upsample=False, Cin2=0):
     ksplit = _halo_splits(ks)
     outs = []
     for mfast in ((1, 0) if ksplit > 1 else (1,)):
-        with tuned({9: ks, 16: knob16, 14: mfast}):
+        with tuned(ksplit=ks, halo=knob16, mfast=mfast):
             outs.append(run_conv(HALO_NIMG, H, W, HALO_CIN, HALO_COUT, ksplit,
                                  lambda: ops.conv3x3(x, HALO_NIMG, H, W, wc, b, upsample=upsample, **kw),
                                  halo=True, tile=(rows, 320), Cin2=Cin2, upsample=upsample, residual=not Cin2))
@@ -486,7 +472,7 @@ def test_halo_knob16_table_is_complete():
     """HALO_PLAIN lists every (geometry, knob 16) pair that takes a halo tile: the pairs left out plan shifted tiles."""
     for (W, H), settings in HALO_PLAIN.items():
         for knob16 in (1, 2, 3):
-            with tuned({16: knob16}):
+            with tuned(halo=knob16):
                 plan = ops.conv_plan(HALO_NIMG, H, W, HALO_CIN, HALO_COUT, residual=True)
             assert plan["halo"] == (knob16 in settings), (W, H, knob16, plan)
             if plan["halo"]:
@@ -523,7 +509,7 @@ def test_halo_groupnorm_conv_nonsquare(W, H, ks):
     ksplit = _halo_splits(ks)
     tile = (HALO_GN[(W, H)], 320)
     for mfast in ((1, 0) if ksplit > 1 else (1,)):
-        with tuned({9: ks, 14: mfast}):
+        with tuned(ksplit=ks, mfast=mfast):
             fused = run_conv(nimg, H, W, Cin, Cout, ksplit,
                              lambda: ops.conv3x3(x, nimg, H, W, wc, b, gn=(sc, sh, True), **kw),
                              halo=True, tile=tile, residual=True, gn=True)

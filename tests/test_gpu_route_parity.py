@@ -20,7 +20,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from sdmoe import ops  # noqa: E402
+from sdmoe import ops, tune  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 sys.path.insert(0, GOLD)
@@ -318,8 +318,6 @@ def test_masked_down_projection_bit_exact_every_unet_shape(model, M, K, N):
 def test_topk_one_token_per_wave_matches_four(M, E, k, nrem):
     """The top-k kernels at one token per wave (M <= 16384, default) and four per wave (sdmoe_tune knob 15 = 4):
     identical selection, masked product and keep bits, on scores quantised to force ties at the k-th place."""
-    from sdmoe import _lib
-    lib = _lib.load()
     g = torch.Generator().manual_seed(M + E)
     esize = 20
     F = E * esize
@@ -329,16 +327,13 @@ def test_topk_one_token_per_wave_matches_four(M, E, k, nrem):
     removed = ops.removed_bits(torch.randperm(E, generator=g)[:nrem].tolist(), E, DEV) if nrem else None
     res = {}
     for tpw in (0, 4):
-        _lib.check(lib.sdmoe_tune(15, tpw), "tune")
-        try:
+        with tune.tuned(topk=tpw):
             Pm = P.clone()
             sel_m = torch.zeros((M, (E + 31) // 32), dtype=torch.int32, device=DEV)
             sel_k = torch.zeros_like(sel_m)
             ops.moe_topk_mask(Pm, score, routing, removed=removed, sel_out=sel_m)
             keep = ops.moe_topk_keep(score, routing, M, removed=removed, sel_out=sel_k)
             res[tpw] = (Pm, sel_m, sel_k, keep)
-        finally:
-            _lib.check(lib.sdmoe_tune(15, 0), "tune")
     for a_, b_ in zip(res[0], res[4]):
         assert torch.equal(a_, b_)
     assert torch.equal(res[0][1], res[0][2])
@@ -359,8 +354,6 @@ def test_topk_keep_quad_kernel(M, E, k, nrem, esize, ld):
     expert id; removed experts score 0 and are never kept): identical keep words and selection bits, on scores
     quantised to force ties, with M tails, strided / unaligned score rows (ld != E; ld % 8 != 0 takes the ballot
     kernel), k = 0 and k = E."""
-    from sdmoe import _lib
-    lib = _lib.load()
     g = torch.Generator().manual_seed(M + 7 * E + k)
     F = E * esize
     routing = ops.Routing(torch.arange(F) // esize, E, k, DEV)
@@ -370,14 +363,11 @@ def test_topk_keep_quad_kernel(M, E, k, nrem, esize, ld):
     removed = ops.removed_bits(rm_list, E, DEV) if nrem else None
     res = {}
     for tpw in (0, 4):
-        _lib.check(lib.sdmoe_tune(15, tpw), "tune")
-        try:
+        with tune.tuned(topk=tpw):
             sel = torch.zeros((M, (E + 31) // 32), dtype=torch.int32, device=DEV)
             keep = ops.moe_topk_keep(score, routing, M, removed=removed, sel_out=sel)
             torch.cuda.synchronize()
             res[tpw] = (sel.cpu(), keep.cpu())
-        finally:
-            _lib.check(lib.sdmoe_tune(15, 0), "tune")
     assert torch.equal(res[0][0], res[4][0])
     assert torch.equal(res[0][1], res[4][1])
     # numpy: stable descending order of the fp16 scores (removed -> 0; -0 == +0), first k are selected
@@ -423,13 +413,8 @@ def test_gelu_every_fp16_input_matches_reference_activation(M, gt320):
     x[torch.arange(M), torch.arange(M) % 64] = 1.0
     w = torch.cat([torch.ones(F, 64, dtype=torch.float16), gate.t().contiguous()], 0).to(DEV)
     w_il, b_il = ops.interleave_geglu(w, torch.zeros(2 * F, dtype=torch.float16, device=DEV), None)
-    from sdmoe import _lib
-    lib = _lib.load()
-    _lib.check(lib.sdmoe_tune(20, gt320), "tune")
-    try:
+    with tune.tuned(gt320=gt320):
         P = ops.linear_geglu(x.to(DEV), w_il, b_il, ops.ACT_GELU).cpu()
-    finally:
-        _lib.check(lib.sdmoe_tune(20, 1), "tune")
     exp_rows = torch.arange(M) % 64
     assert torch.equal(P, got_u[exp_rows])                    # fused == unfused, bit for bit
     same = (got_u.view(torch.int16) == ref.view(torch.int16)) | ((got_u == 0) & (ref == 0))

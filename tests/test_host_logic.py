@@ -501,11 +501,13 @@ def test_conv_weight_with_shortcut_layout():
 
 
 def test_sdmoe_tune_env_is_parsed_at_load(monkeypatch):
-    """SDMOE_TUNE="knob=value,..." applies sdmoe_tune at library load; a bad knob raises."""
-    from sdmoe import _lib
+    """SDMOE_TUNE="knob=value,..." applies sdmoe_tune at library load, knobs by id or by name; a bad knob raises."""
+    from sdmoe import _lib, tune
     monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setenv("SDMOE_TUNE", "1=0,0=0")
+    monkeypatch.setenv("SDMOE_TUNE", "1=0,0=0,halo=2")
     assert _lib.load() is not None
+    assert tune.knobs()["halo"] == (16, 1, 2)
+    tune.reset()
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setenv("SDMOE_TUNE", "99=1")
     with pytest.raises(_lib.SdmoeError):
@@ -519,6 +521,10 @@ def test_sdmoe_tune_env_is_parsed_at_load(monkeypatch):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.delenv("SDMOE_TUNE")
     _lib.load()
+    assert _lib.parse_tune(" tile=0, 16=2,,") == [(1, 0), (16, 2)]
+    with pytest.raises(_lib.SdmoeError, match="no knob named 'tiles'"):
+        _lib.parse_tune("tiles=1")
+    _assert_knobs_at_defaults()
 
 
 def test_bench_roofline_timer_samples_whole_evaluations():
@@ -643,8 +649,7 @@ def test_masked_gemm_plans_take_the_plain_split():
     # the tile of a masked mode is the one masked_tile() (csrc/gemm.hip) maps the plain tile to: the same tile, except
     # that the tiles not built for the masked modes (128x320, 64x320, 8-wave 128x160, 128x32) fall to 128x160 (N % 160
     # == 0) or 128x128, and the keep-masked A operand runs 256x320 on 4x2 waves. Every one walks K in 64-deep steps.
-    from sdmoe import _lib
-    lib = _lib.load()
+    from sdmoe import tune
 
     def expect(mode, plain, N):
         tile, waves = plain["tile"], plain["waves"]
@@ -655,18 +660,15 @@ def test_masked_gemm_plans_take_the_plain_split():
         return tile, waves
 
     seen = set()
-    try:
-        for knob1, M, N, K in ((0, 16384, 640, 640), (0, 8192, 640, 640), (8, 4096, 320, 1280), (8, 512, 640, 640),
-                               (7, 2048, 320, 1280), (0, 65536, 320, 1280), (0, 65536, 640, 2560), (0, 1000, 1280, 5120)):
-            assert lib.sdmoe_tune(1, knob1) == 0
+    for knob1, M, N, K in ((0, 16384, 640, 640), (0, 8192, 640, 640), (8, 4096, 320, 1280), (8, 512, 640, 640),
+                           (7, 2048, 320, 1280), (0, 65536, 320, 1280), (0, 65536, 640, 2560), (0, 1000, 1280, 5120)):
+        with tune.tuned(tile=knob1):
             plain = ops.gemm_plan("plain", M, N, K)
             seen.add((plain["tile"], plain["waves"]))
             for mode in ("keep", "wmask", "keepw"):
                 got = ops.gemm_plan(mode, M, N, K)
                 assert (got["tile"], got["waves"]) == expect(mode, plain, N), (mode, knob1, M, N, K, got, plain)
                 assert got["ksplit"] == plain["ksplit"]
-    finally:
-        lib.sdmoe_tune(1, 0)
     assert {((128, 320), (2, 4)), ((64, 320), (2, 4)), ((256, 320), (2, 4)), ((128, 160), (4, 2))} <= seen
 
 
@@ -695,7 +697,7 @@ def test_conv_and_geglu_launch_plans():
     planners existed (256 CUs, the default workspace), so a change of any tile, ring depth or split shows here; and the
     split invariants hold over a grid of conv shapes and workspace sizes."""
     from unet_shapes import conv3x3_shapes, geglu_projection_shapes
-    from sdmoe import ops, _lib
+    from sdmoe import ops, _lib, tune
     table = _launch_plan_table()
     convs = conv3x3_shapes("sd14") + conv3x3_shapes("sdxl")
     assert (32, 64, 320, 0, 320, 1, 0, 0) in convs      # 64x64 320 -> 320 at 32 images
@@ -749,11 +751,8 @@ def test_conv_and_geglu_launch_plans():
             else:
                 assert bk == 64 and stages in (2, 3) and kchunk2 == 0, what
         assert nhalo > 1000
-    try:
-        assert lib.sdmoe_tune(16, 0) == 0
+    with tune.tuned(halo=0):
         assert not any(p[0] for *_, p in grid_plans(ops.WS_FLOATS))
-    finally:
-        lib.sdmoe_tune(16, 1)
 
 
 def test_conv_gn_fusable_agrees_with_the_library(monkeypatch):
@@ -780,22 +779,167 @@ def test_forced_split_counts_leave_no_empty_split():
     split and as many splits as that takes: ceil(nk / ceil(nk / min(ks, nk))) -- the count tests/test_gpu_launch_space.py
     expects of every forced launch. A workspace of s slabs lowers the wanted count to s first, so never more than s
     splits come out."""
-    from sdmoe import ops, _lib
-    lib = _lib.load()
+    from sdmoe import ops, tune
 
     def splits(nk, ks):
         kchunk = -(-nk // min(ks, nk))
         return -(-nk // kchunk)
 
     M, N = 64, 320
-    try:
-        for ks in range(1, 33):
-            assert lib.sdmoe_tune(9, ks) == 0
+    for ks in range(1, 33):
+        with tune.tuned(ksplit=ks):
             for nk in range(1, 25):
                 assert ops.gemm_plan("plain", M, N, 64 * nk)["ksplit"] == splits(nk, ks), (nk, ks)
                 for s in (1, 2, 3, 4, 7, 11, 24):
                     got = ops.gemm_plan("plain", M, N, 64 * nk, workspace_floats=s * M * N)["ksplit"]
                     assert got <= s and got == splits(nk, min(ks, s)), (nk, ks, s, got)
                 assert ops.gemm_plan("plain", M, N, 64 * nk, workspace_floats=0)["ksplit"] == 1
+    _assert_knobs_at_defaults()
+
+
+# ---- the knob table (csrc/tune.hip). The ABI contract, transcribed from sdmoe_tune as it stood before the table:
+# id -> (name, default, legal values)
+KNOB_ABI = {
+    0: ("stages", 0, {0, 2, 3}),
+    1: ("tile", 0, set(range(9))),
+    4: ("attn", 0, {0, 1, 2, 4, 8, 9}),
+    6: ("diag", 0, set(range(64))),
+    7: ("gn_fused", 1, {0, 1, 2}),
+    8: ("res16", 1, {0, 1}),
+    9: ("ksplit", 0, set(range(33))),
+    14: ("mfast", 1, {0, 1}),
+    15: ("topk", 0, {0, 1, 4}),
+    16: ("halo", 1, {0, 1, 2, 3}),
+    20: ("gt320", 1, {0, 1}),
+    21: ("narrow", 1, {0, 1}),
+    23: ("epi_direct", 1, {0, 1, 2}),
+}
+
+
+def _assert_knobs_at_defaults():
+    from sdmoe import _lib
+    for kid, name, dflt, val in _lib.knob_table():  # sdmoe_tune_knob(0..) until it refuses the index
+        assert val == dflt == KNOB_ABI[kid][1], (name, val, dflt)
+
+
+def test_knob_table_contents():
+    """The table enumerates exactly the thirteen knobs, each once, under unique names, with the ABI's defaults."""
+    from sdmoe import _lib, tune
+    rows = _lib.knob_table()
+    assert sorted(r[0] for r in rows) == sorted(KNOB_ABI) and len(rows) == 13
+    assert len({r[1] for r in rows}) == 13
+    for kid, name, dflt, _ in rows:
+        assert (name, dflt) == KNOB_ABI[kid][:2]
+    assert [r[0] for r in rows if r[2] == 0] == [0, 1, 4, 6, 9, 15]
+    assert [r[0] for r in rows if r[2] == 1] == [7, 8, 14, 16, 20, 21, 23]
+    assert tune.knobs() == {name: (kid, dflt, val) for kid, name, dflt, val in rows}
+    _assert_knobs_at_defaults()
+
+
+def test_knob_enumerator_argument_errors():
+    from sdmoe import _lib
+    lib = _lib.load()
+    i, s = ctypes.c_int(), ctypes.c_char_p()
+    assert lib.sdmoe_tune_knob(0, i, s, i, i) == 0 and lib.sdmoe_tune_knob(12, i, s, i, i) == 0
+    assert lib.sdmoe_tune_knob(13, i, s, i, i) == -1 and lib.sdmoe_tune_knob(-1, i, s, i, i) == -1
+    for null in range(4):
+        args = [i, s, i, i]
+        args[null] = None
+        assert lib.sdmoe_tune_knob(0, *args) == -1
+    _assert_knobs_at_defaults()
+
+
+def test_sdmoe_tune_accepts_exactly_the_legal_values():
+    """For every id 0..31 and value -2..65, sdmoe_tune returns 0 exactly for a legal value of a knob of the table, else
+    -1; an accepted call is what the enumerator then reports, a rejected one leaves the value as it was."""
+    from sdmoe import _lib
+    lib = _lib.load()
+
+    def value_of(kid):
+        return {r[0]: r[3] for r in _lib.knob_table()}.get(kid)
+
+    try:
+        for kid in range(32):
+            legal = KNOB_ABI[kid][2] if kid in KNOB_ABI else set()
+            for value in range(-2, 66):
+                before = value_of(kid)
+                st = lib.sdmoe_tune(kid, value)
+                assert st == (0 if value in legal else -1), (kid, value, st)
+                assert value_of(kid) == (value if value in legal else before), (kid, value)
+        for value in (64, 127, 128, (1 << 31) - 1, -(1 << 31)):  # past the 64-bit mask of legal values
+            assert lib.sdmoe_tune(6, value) == -1 and value_of(6) == 63, value
     finally:
-        lib.sdmoe_tune(9, 0)
+        assert lib.sdmoe_tune_reset() == 0
+    _assert_knobs_at_defaults()
+
+
+def test_sdmoe_tune_reset_restores_every_default():
+    from sdmoe import _lib
+    lib = _lib.load()
+    try:
+        for kid, (_, dflt, legal) in KNOB_ABI.items():
+            assert lib.sdmoe_tune(kid, max(legal - {dflt})) == 0
+        assert all(val != dflt for _, _, dflt, val in _lib.knob_table())
+    finally:
+        assert lib.sdmoe_tune_reset() == 0
+    _assert_knobs_at_defaults()
+
+
+def test_tuned_restores_the_previous_values():
+    """tune.tuned puts back what was set before it, not the default; also when the block raises, when a value in it is
+    refused, and nested."""
+    from sdmoe import _lib, tune
+
+    def values(*names):
+        table = tune.knobs()
+        return tuple(table[n][2] for n in names)
+
+    try:
+        tune.set(halo=2)
+        with tune.tuned(halo=0):
+            assert values("halo") == (0,)
+        assert values("halo") == (2,)
+        with pytest.raises(ZeroDivisionError):
+            with tune.tuned(halo=3, ksplit=5):
+                assert values("halo", "ksplit") == (3, 5)
+                1 / 0
+        assert values("halo", "ksplit") == (2, 0)
+        with tune.tuned(ksplit=4, tile=3):
+            with tune.tuned(ksplit=7, halo=1):
+                assert values("ksplit", "tile", "halo") == (7, 3, 1)
+                with tune.tuned(ksplit=1):
+                    assert values("ksplit") == (1,)
+                assert values("ksplit") == (7,)
+            assert values("ksplit", "tile", "halo") == (4, 3, 2)
+        assert values("ksplit", "tile", "halo") == (0, 0, 2)
+        # a refused value or an unknown name raises and leaves every knob as it was, the ones set before it included
+        with pytest.raises(_lib.SdmoeError):
+            with tune.tuned(ksplit=9, stages=1):
+                raise AssertionError("entered")
+        with pytest.raises(_lib.SdmoeError, match="no knob named 'split'"):
+            with tune.tuned(tile=2, split=2):
+                raise AssertionError("entered")
+        assert values("ksplit", "stages", "tile", "halo") == (0, 0, 0, 2)
+        tune.reset()
+        assert values("halo") == (1,)
+    finally:
+        tune.reset()
+    _assert_knobs_at_defaults()
+
+
+def test_knob_names_need_a_library_with_the_table(monkeypatch):
+    """An SDMOE_AB=1 library from before sdmoe_tune_knob: knobs by id still parse (and go through plain sdmoe_tune),
+    a name, tune.knobs() and tune.tuned() raise an error that says why. No table is kept in Python."""
+    from sdmoe import _lib, tune
+    _lib.load()
+    monkeypatch.setattr(_lib, "has", lambda lib, name: name != "sdmoe_tune_knob")
+    assert _lib.parse_tune("1=0,16=2") == [(1, 0), (16, 2)]
+    with pytest.raises(_lib.SdmoeError, match="no sdmoe_tune_knob"):
+        _lib.parse_tune("tile=0")
+    with pytest.raises(_lib.SdmoeError, match="no sdmoe_tune_knob"):
+        tune.knobs()
+    with pytest.raises(_lib.SdmoeError, match="no sdmoe_tune_knob"):
+        with tune.tuned(tile=1):
+            raise AssertionError("entered")
+    monkeypatch.undo()
+    _assert_knobs_at_defaults()

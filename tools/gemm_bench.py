@@ -9,7 +9,7 @@ sys.path[:0] = [os.path.join(ROOT, "diffusion-models-moe_amd"), ROOT]
 
 import torch  # noqa: E402
 
-from sdmoe import ops  # noqa: E402
+from sdmoe import ops, tune  # noqa: E402
 
 
 def timeit(fn, iters):
@@ -35,11 +35,7 @@ def main():
     ap.add_argument("--nqf", type=int, default=0, help="attention kernel (knob 4): 0 = auto, 1 = 32x32x16, 2/4 = 16x16x32 NQF")
     ap.add_argument("--diag", type=int, default=0, help="GEMM diagnostics (knob 6, bits): 1 = no K-loop loads, 2 = no MFMA, 4 = no epilogue")
     a = ap.parse_args()
-    from sdmoe import _lib
-    _lib.check(_lib.load().sdmoe_tune(0, a.stages), "tune")
-    _lib.check(_lib.load().sdmoe_tune(1, a.tile), "tune")
-    _lib.check(_lib.load().sdmoe_tune(4, a.nqf), "tune")
-    _lib.check(_lib.load().sdmoe_tune(6, a.diag), "tune")
+    tune.set(stages=a.stages, tile=a.tile, attn=a.nqf, diag=a.diag)
     print("stages", a.stages, "tile", a.tile)
     n = a.nimg
     dev = "cuda"

@@ -9,7 +9,7 @@ sys.path[:0] = [os.path.join(ROOT, "diffusion-models-moe_amd"), ROOT]
 
 import torch  # noqa: E402
 
-from sdmoe import ops  # noqa: E402
+from sdmoe import ops, tune  # noqa: E402
 
 
 def main():
@@ -19,12 +19,10 @@ def main():
     ap.add_argument("--nimg", type=int, default=16)
     ap.add_argument("--diag", type=int, default=0, help="GEMM diagnostics bits (sdmoe_tune knob 6)")
     ap.add_argument("--d", type=int, default=40, help="attn: head dim (8 heads, N = 4096)")
-    ap.add_argument("--tune", default="", help="extra sdmoe_tune settings 'knob=value,...'")
+    ap.add_argument("--tune", default="", help="extra sdmoe_tune settings 'knob=value,...' (ids or names)")
     a = ap.parse_args()
-    from sdmoe import _lib
-    _lib.check(_lib.load().sdmoe_tune(6, a.diag), "tune")
-    for k, v in _lib.parse_tune(a.tune):
-        _lib.check(_lib.load().sdmoe_tune(k, v), "tune")
+    tune.set(diag=a.diag)
+    tune.set(**tune.parse(a.tune))
     n, dev = a.nimg, "cuda"
     if a.what == "attn":
         C = 8 * a.d

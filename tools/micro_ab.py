@@ -12,13 +12,10 @@ sys.path[:0] = [os.path.join(ROOT, "diffusion-models-moe_amd"), ROOT]
 
 import torch  # noqa: E402
 
-from sdmoe import _lib, ops  # noqa: E402
+from sdmoe import ops, tune  # noqa: E402
 
 DEV = "cuda"
 N_IMG = 16
-
-
-DEFAULTS = {"7": 1, "8": 1, "14": 1, "16": 1, "20": 1, "21": 1, "23": 1}  # sdmoe_tune knobs whose default is not 0
 
 
 def rnd(*shape, scale=1.0):
@@ -160,7 +157,6 @@ def main():
     a = ap.parse_args()
     global N_IMG
     N_IMG = a.nimg
-    lib = _lib.load()
     fam = {"gn": gn_cases, "linear": linear_cases, "geglu": geglu_cases, "conv": conv_cases, "attn": attn_cases,
            "topk": topk_cases, "keep": keep_cases}
     cases = [c for k in (fam if a.family == "all" else [a.family]) for c in fam[k]()]
@@ -168,11 +164,8 @@ def main():
     table = {}
     for rep in range(2):  # interleaved twice
         for st in settings:
-            for k, v in _lib.parse_tune(st):
-                _lib.check(lib.sdmoe_tune(k, v), "tune")
-            r = run(cases, a.iters)
-            for k, _ in _lib.parse_tune(st):  # back to defaults (0) unless the knob's default differs
-                _lib.check(lib.sdmoe_tune(k, DEFAULTS.get(str(k), 0)), "tune")
+            with tune.tuned(**tune.parse(st)):
+                r = run(cases, a.iters)
             for name, v in r.items():
                 table.setdefault(name, {}).setdefault(st, []).append(v)
     for name, per in table.items():

@@ -12,7 +12,7 @@ sys.path[:0] = [os.path.join(ROOT, "diffusion-models-moe_amd"), ROOT]
 
 import torch  # noqa: E402
 
-from sdmoe import _lib, ops  # noqa: E402
+from sdmoe import ops, tune  # noqa: E402
 
 DEV = "cuda"
 N_IMG = 16
@@ -88,7 +88,6 @@ def main():
     ap.add_argument("--cfgs", default="0:0:0 1:2:0 1:3:0 2:2:0 2:3:0 3:0:0 4:0:0 5:0:0 6:0:0 7:2:0 7:3:0 8:2:0 8:3:0")
     ap.add_argument("--iters", type=int, default=30)
     a = ap.parse_args()
-    lib = _lib.load()
     cfgs = [tuple(int(v) for v in c.split(":")) for c in a.cfgs.split()]
     only = [o for o in a.only.split("|") if o]
     for name, fn, flop in cases():
@@ -98,21 +97,16 @@ def main():
         ref = None
         bad = []
         for t, st, ks in cfgs:
-            _lib.check(lib.sdmoe_tune(1, t), "tile")
-            _lib.check(lib.sdmoe_tune(0, st), "stages")
-            _lib.check(lib.sdmoe_tune(9, ks), "ksplit")
-            y = fn()
-            torch.cuda.synchronize()
-            if ref is None:
-                ref = y.float().clone()
-            else:  # every config must compute the same product (fp32 accumulation order may differ)
-                err = ((y.float() - ref).norm() / ref.norm()).item()
-                if not err < 1e-3:
-                    bad.append(f"{t}:{st}:{ks} rel {err:.2e}")
-            res.append((time_us(fn, a.iters), t, st, ks))
-        _lib.check(lib.sdmoe_tune(1, 0), "tile")
-        _lib.check(lib.sdmoe_tune(0, 0), "stages")
-        _lib.check(lib.sdmoe_tune(9, 0), "ksplit")
+            with tune.tuned(tile=t, stages=st, ksplit=ks):
+                y = fn()
+                torch.cuda.synchronize()
+                if ref is None:
+                    ref = y.float().clone()
+                else:  # every config must compute the same product (fp32 accumulation order may differ)
+                    err = ((y.float() - ref).norm() / ref.norm()).item()
+                    if not err < 1e-3:
+                        bad.append(f"{t}:{st}:{ks} rel {err:.2e}")
+                res.append((time_us(fn, a.iters), t, st, ks))
         auto = res[0][0]
         best = min(res)
         line = "  ".join(f"{t}:{st}:{ks}={us:.1f}" for us, t, st, ks in res)
