@@ -63,6 +63,10 @@ struct GemmParams {
   // wmask[(k / 64) * N * 8 + n * 8 + (k % 64) / 8] bit (k % 8) SET = W[n, k] removed (zeroed on the B fragments)
   const uint8_t* wmask;
   int wmask_bytes;
+  // one Wanda mask per image (sdmoe_linear_masked_sets): image i = m / rows_per_batch takes the mask at wmask +
+  // image_set[i] * wset_bytes (wmask_bytes = the extent of ONE set); null = the one mask at wmask
+  const int* image_set;
+  long wset_bytes;
   // LayerNorm folded into the GEMM (MODE_GEMM_LN / MODE_GEGLU_LN): C = rstd_m * (A W'^T - mean_m * wsum) + ln_bias
   // with W' = W diag(gamma) (fp16), wsum[n] = sum_k W'[n, k], ln_bias[n] = bias[n] + sum_k W[n, k] beta[k] (fp32,
   // sdmoe_ln_fold); mean_m / rstd_m over the K = C channels of row m, accumulated from the A tiles in LDS
@@ -366,8 +370,14 @@ __global__ __launch_bounds__(64 * WMW * WNW, (NSTAGE == 2 && (WMW * WNW == 4 || 
   // and the counted vmcnt waits stay uniform
   const int kpiece = KEEP && wave < K_INS ? wave : 0;
   const bool kpa = AKEEP && kpiece < KA_INS;  // wave-uniform: this wave's piece is A keep bytes (else W mask bytes)
+  // per-image mask sets (sdmoe_linear_masked_sets): the tile's image picks the base of its set's mask -- one scalar
+  // load per workgroup; a tile never straddles two images (host check rows_per_batch % BM)
+  const uint8_t* wmask = p.wmask;
+  if constexpr (WKEEP) {
+    if (p.image_set) wmask += (long)p.image_set[m0 / p.rows_per_batch] * p.wset_bytes;
+  }
   const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc(
-      kpa ? (void*)p.keep : (void*)p.wmask, (short)0, KEEP ? (kpa ? p.keep_bytes : p.wmask_bytes) : 0, 0x00020000);
+      kpa ? (void*)p.keep : (void*)wmask, (short)0, KEEP ? (kpa ? p.keep_bytes : p.wmask_bytes) : 0, 0x00020000);
   const unsigned kstride = kpa ? (unsigned)p.M * 8u : (unsigned)p.N * 8u;  // bytes per K-step of the mask layout
   unsigned kvoff = OOB;
   int kdst = KEEP_OFF;
@@ -1696,6 +1706,19 @@ Plan plan_launch(int mode, const GemmParams& p, bool ws, long ws_floats) {
   return tile_plan(mode, masked ? masked_tile(mode, r.tile, p) : r.tile, p, ksplit, r.stages_want);
 }
 
+// plan of a masked launch with one Wanda mask per rows_per_img-row image (sdmoe_linear_masked_sets): the shape's own
+// masked plan where its tile's rows divide an image -- tile and split, hence the bits, of sdmoe_linear_masked -- else a
+// 64-row tile (built for every masked mode) with plan_split's split for THAT tile; false = rows_per_img % 64 != 0, a
+// tile would straddle two images' masks
+bool plan_sets(int mode, const GemmParams& p, int rows_per_img, bool ws, long ws_floats, Plan* pl) {
+  *pl = plan_launch(mode, p, ws, ws_floats);
+  if (rows_per_img % kTile[pl->tile].bm == 0) return true;
+  if (rows_per_img % 64) return false;
+  const int tile = p.N % 160 == 0 ? T64x160 : T64x128;
+  *pl = tile_plan(mode, tile, p, plan_split(kTile[tile], MODE_GEMM, p, ws, ws_floats, 0), 0);
+  return true;
+}
+
 // plan of a 3x3 conv: halo tiles where plan_halo takes the shape, else shifted tiles
 Plan plan_conv(const GemmParams& p, bool ws, long ws_floats) {
   Plan pl;
@@ -1729,6 +1752,7 @@ constexpr auto kLaunch = launch_table(std::make_integer_sequence<int, NMODE * NT
 int launch(const Plan& pl, GemmParams p, float* ws, hipStream_t s) {
   const TileShape& t = kTile[pl.tile];
   if (p.w_bstride && p.rows_per_batch % t.bm) return SDMOE_EUNSUP;  // a tile would straddle two images' weights
+  if (p.image_set && p.rows_per_batch % t.bm) return SDMOE_EUNSUP;  // ... or two images' Wanda masks
   if (pl.ksplit > 1 && !ws) return SDMOE_EARG;
   p.ksplit = pl.ksplit; p.kchunk = pl.kchunk; p.kchunk2 = pl.kchunk2; p.mfast = pl.mfast;
   p.part = pl.ksplit > 1 ? ws : nullptr;
@@ -1815,6 +1839,26 @@ __global__ __launch_bounds__(256) void wmask_kmajor_kernel(const uint8_t* __rest
       for (int b = 0; b < 8; ++b) w |= (unsigned long long)row[8 * s + b] << (8 * b);
     }
     out[id] = w;
+  }
+}
+
+// Unions of concept masks (sdmoe_wmask_union_sets): out[s][w] = OR of masks[c][w] over the concepts c whose bit is set
+// in select[s]; one thread per output word, the concepts' words streamed (sets of one launch re-read them from L2)
+__global__ __launch_bounds__(256) void wmask_union_sets_kernel(const unsigned long long* __restrict__ masks,
+                                                               long mask_stride, const unsigned* __restrict__ select,
+                                                               unsigned cmask, int nsets, long words,
+                                                               unsigned long long* __restrict__ out) {
+  const long n = (long)nsets * words;
+  for (long id = blockIdx.x * 256L + threadIdx.x; id < n; id += (long)gridDim.x * 256) {
+    const long s = id / words, w = id - s * words;
+    unsigned sel = select[s] & cmask;  // (bits past nconcepts name no mask)
+    unsigned long long acc = 0;
+    while (sel) {
+      const int c = __builtin_ctz(sel);
+      sel &= sel - 1;
+      acc |= masks[c * mask_stride + w];
+    }
+    out[id] = acc;
   }
 }
 
@@ -2022,6 +2066,55 @@ extern "C" int sdmoe_gemm_plan(int mode, int M, int N, int K, int has_residual, 
   else return SDMOE_EUNSUP;
   const TileShape& t = kTile[pl.tile];
   out[0] = t.bm; out[1] = t.bn; out[2] = t.wmw; out[3] = t.wnw; out[4] = pl.ksplit;
+  return SDMOE_OK;
+}
+
+extern "C" int sdmoe_linear_masked_sets(const void* A, long lda, const void* keep, const void* W, long ldw,
+                                        const void* wmasks, long set_stride, const int* image_set, int nsets,
+                                        int rows_per_img, const void* bias, const void* R, long ldr, void* C, long ldc,
+                                        int M, int N, int K, float* workspace, long workspace_floats, void* stream) {
+  if (M == 0) return SDMOE_OK;
+  if (!A || !W || !C || !wmasks || !image_set || M < 0 || N <= 0 || K <= 0 || nsets <= 0 || rows_per_img <= 0)
+    return SDMOE_EARG;
+  if (K % 64 || N % 8 || lda % 8 || ldw % 8 || ldc % 8 || (R && ldr % 8) || M % rows_per_img) return SDMOE_ESHAPE;
+  GemmParams p{};
+  if (const int st = fill_linear(p, A, lda, W, ldw, bias, R, ldr, C, ldc, M, N, K, ACT_NONE)) return st;
+  const long kb = (long)(K / 64) * M * 8, mb = (long)(K / 64) * N * 8;
+  if (kb >= (long)OOB || mb >= (long)OOB) return SDMOE_ESHAPE;
+  if (set_stride < mb / 8) return SDMOE_EARG;  // (sets would overlap)
+  p.keep = (const uint8_t*)keep; p.keep_bytes = keep ? (int)kb : 0;
+  p.wmask = (const uint8_t*)wmasks; p.wmask_bytes = (int)mb;
+  p.image_set = image_set; p.wset_bytes = set_stride * 8; p.rows_per_batch = rows_per_img;
+  Plan pl;
+  if (!plan_sets(keep ? MODE_KEEPW : MODE_WMASK, p, rows_per_img, workspace, workspace_floats, &pl)) return SDMOE_EUNSUP;
+  return launch(pl, p, workspace, (hipStream_t)stream);
+}
+
+extern "C" int sdmoe_gemm_plan_sets(int has_keep, int M, int N, int K, int rows_per_img, int has_residual,
+                                    long workspace_floats, int* out) {
+  if (!out || M <= 0 || N <= 0 || K <= 0 || rows_per_img <= 0 || workspace_floats < 0) return SDMOE_EARG;
+  if (K % 64 || N % 8 || M % rows_per_img) return SDMOE_ESHAPE;
+  GemmParams p{};
+  p.M = M; p.N = N; p.K = K; p.act = ACT_NONE; p.rows_per_batch = rows_per_img;
+  p.R = has_residual ? reinterpret_cast<const half_t*>(out) : nullptr;  // (only its presence enters the plan)
+  Plan pl;
+  if (!plan_sets(has_keep ? MODE_KEEPW : MODE_WMASK, p, rows_per_img, workspace_floats > 0, workspace_floats, &pl))
+    return SDMOE_EUNSUP;
+  const TileShape& t = kTile[pl.tile];
+  out[0] = t.bm; out[1] = t.bn; out[2] = t.wmw; out[3] = t.wnw; out[4] = pl.ksplit;
+  return SDMOE_OK;
+}
+
+extern "C" int sdmoe_wmask_union_sets(const void* masks, long mask_stride, int nconcepts, const unsigned* select,
+                                      int nsets, long words, void* out, void* stream) {
+  if (nsets == 0 || words == 0) return SDMOE_OK;
+  if (!select || !out || nsets < 0 || words < 0 || nconcepts < 0 || nconcepts > 32 || (nconcepts && !masks) ||
+      mask_stride < words)
+    return SDMOE_EARG;
+  const unsigned cmask = nconcepts == 32 ? ~0u : (1u << nconcepts) - 1u;
+  wmask_union_sets_kernel<<<grid_for((long)nsets * words), 256, 0, (hipStream_t)stream>>>(
+      (const unsigned long long*)masks, mask_stride, select, cmask, nsets, words, (unsigned long long*)out);
+  SDMOE_CHECK_LAUNCH();
   return SDMOE_OK;
 }
 

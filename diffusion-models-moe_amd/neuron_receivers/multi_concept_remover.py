@@ -10,6 +10,8 @@ remove_concepts keeps the reference's two-value contract (:55-99; unified_editin
 (stitched, singles) where `stitched` is [before | after] side by side along the width -- the tensor form of the
 PIL paste at :83-99 (latents, or RGB when the pipeline decodes) -- and `singles` the same pair per concept (None for
 one concept). The unstitched images of the last call are kept in `self.last_outputs`.
+remove_concepts_batch (not in the reference) runs the removal of a whole batch of prompts, each with its own concept
+list, in one pipeline call: the loop of benchmarks/unified_editing.py:106-126 as one batched call.
 """
 from __future__ import annotations
 
@@ -42,6 +44,7 @@ class MultiConceptRemoverWanda:
         self.union_neuron_remover = WandaRemoveNeuronsFast.from_packed(seed, start, T, n_layers, replace_fn=replace_fn,
                                                                        keep_nsfw=keep_nsfw)
         self.last_outputs = None
+        self.per_prompt_remover = None  # WandaRemovePerPrompt over self.removers, built by remove_concepts_batch
 
     def reset_union_remover(self):
         u = self.union_neuron_remover
@@ -71,6 +74,23 @@ class MultiConceptRemoverWanda:
             return np.concatenate([before, after], axis=-2)
         raise TypeError(f"cannot stitch {type(before).__name__} and {type(after).__name__}: expected two torch "
                         f"tensors (CHW / latents) or two numpy HWC arrays")
+
+    def remove_concepts_batch(self, model, prompts, concepts_per_prompt):
+        """The removal images of remove_concepts for a whole batch in ONE pipeline call: prompt i with the union of
+        exactly concepts_per_prompt[i] (an empty list = the unedited image), through WandaRemovePerPrompt. Returns the
+        list of removal images in prompt order. Prompt i starts from the latents of global prompt index
+        model.prompt_offset + i, as any batched call. The shared union remover is neither used nor changed."""
+        from neuron_receivers.remove_wanda_per_prompt import WandaRemovePerPrompt
+        prompts = [prompts] if isinstance(prompts, str) else list(prompts)
+        if len(prompts) != len(concepts_per_prompt):
+            raise ValueError(f"{len(prompts)} prompts but {len(concepts_per_prompt)} concept lists")
+        rec = self.per_prompt_remover
+        if rec is None or list(rec.removers.values()) != list(self.removers.values()):
+            rec = self.per_prompt_remover = WandaRemovePerPrompt(self.removers, seed=self.seed, store_gates=False)
+        rec.set_prompt_concepts(concepts_per_prompt)
+        rec.reset_time_layer()
+        out, _ = rec.observe_activation(model, prompts)
+        return list(out)
 
     def remove_concepts(self, model, prompt, concepts):
         """Returns (stitched [original | union removed], per-concept stitched pairs or None) -- two values, as the

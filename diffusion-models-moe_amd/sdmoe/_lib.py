@@ -42,6 +42,9 @@ SIGNATURES = {
     "sdmoe_moe_topk_keep": [_I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P],
     "sdmoe_linear_keep": [_P, _L, _P, _P, _L, _P, _P, _L, _P, _L, _I, _I, _I, _P, _L, _P],
     "sdmoe_linear_masked": [_P, _L, _P, _P, _L, _P, _P, _P, _L, _P, _L, _I, _I, _I, _P, _L, _P],
+    "sdmoe_linear_masked_sets": [_P, _L, _P, _P, _L, _P, _L, _P, _I, _I, _P, _P, _L, _P, _L, _I, _I, _I, _P, _L, _P],
+    "sdmoe_gemm_plan_sets": [_I, _I, _I, _I, _I, _I, _L, _P],
+    "sdmoe_wmask_union_sets": [_P, _L, _I, _P, _I, _L, _P, _P],
     "sdmoe_gemm_plan": [_I, _I, _I, _I, _I, _I, _L, _P],
     "sdmoe_conv_plan": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _P],
     "sdmoe_wmask_kmajor": [_P, _L, _I, _I, _P, _P, _P],

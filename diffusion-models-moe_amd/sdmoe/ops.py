@@ -183,6 +183,116 @@ def linear_masked(x, w, bias=None, *, keep=None, wmask=None, residual=None, out=
     return out
 
 
+def gemm_plan_sets(M, N, K, rows_per_img, *, keep=False, residual=False, workspace_floats=WS_FLOATS):
+    """The launch sdmoe_linear_masked_sets would make (sdmoe_gemm_plan_sets; queries the CU count as gemm_plan does):
+    the same dict as gemm_plan, its tile rows dividing rows_per_img. SdmoeError where the launch would refuse
+    (rows_per_img % 64 != 0 and the shape's own tile straddles images): linear_masked_sets then runs per image run."""
+    lib = _lib.load()
+    out = (ctypes.c_int * 5)()
+    _lib.check(lib.sdmoe_gemm_plan_sets(int(bool(keep)), M, N, K, rows_per_img, int(bool(residual)), workspace_floats,
+                                        out), "sdmoe_gemm_plan_sets")
+    return {"tile": (out[0], out[1]), "waves": (out[2], out[3]), "ksplit": out[4]}
+
+
+def wmask_union_sets(masks, select, out=None):
+    """out[s] = OR of masks[c] over the concepts c with bit c of select[s] set (sdmoe_wmask_union_sets): masks int64
+    [nconcepts <= 32, ...] (any trailing shape, e.g. wmask_kmajor's [K/64, N]), select int32 [nsets] (bit patterns of
+    uint32 words); returns int64 [nsets, ...]. select[s] == 0 gives the all-zero (unmasked) set."""
+    lib = _lib.load()
+    if masks.dim() < 2 or masks.dtype != torch.int64:
+        raise ValueError(f"masks must be int64 [nconcepts, ...], got {masks.dtype} {tuple(masks.shape)}")
+    if masks.shape[0] > 32:
+        raise ValueError(f"at most 32 concepts, got {masks.shape[0]}")
+    if select.dim() != 1 or select.dtype != torch.int32:
+        raise ValueError(f"select must be int32 [nsets], got {select.dtype} {tuple(select.shape)}")
+    nc, nsets = masks.shape[0], select.shape[0]
+    words = masks[0].numel()
+    if out is None:
+        out = torch.empty((nsets,) + tuple(masks.shape[1:]), dtype=torch.int64, device=masks.device)
+    elif out.dtype != torch.int64 or out.numel() != nsets * words:
+        raise ValueError(f"out must be int64 with {nsets * words} words, got {out.dtype} {tuple(out.shape)}")
+    st = lib.sdmoe_wmask_union_sets(_dev(masks, "masks", torch.int64), words, nc, _dev(select, "select", torch.int32),
+                                    nsets, words, _dev(out, "out", torch.int64), _stream())
+    _lib.check(st, "sdmoe_wmask_union_sets")
+    return out
+
+
+def image_set_runs(image_set):
+    """Maximal runs of consecutive images sharing a set: [(first image, one past the last, set id)]."""
+    runs = []
+    for i, s in enumerate(image_set):
+        if runs and runs[-1][2] == s:
+            runs[-1] = (runs[-1][0], i + 1, s)
+        else:
+            runs.append((i, i + 1, s))
+    return runs
+
+
+def linear_masked_sets(x, w, bias=None, *, wmasks, image_set, rows_per_img, keep=None, residual=None, out=None,
+                       image_set_dev=None):
+    """out[m] = (x[m] ⊙ keep[m]) @ (w ⊙ (1 - wmasks[image_set[m // rows_per_img]]))^T + bias + residual[m]
+    (sdmoe_linear_masked_sets): linear_masked with one Wanda mask per image. wmasks int64 [nsets, K/64, N]
+    (wmask_union_sets / stacked wmask_kmajor), image_set the set id of every image: a host sequence of ints (checked
+    against nsets here, uploaded per call unless image_set_dev, its int32 device copy, comes with it) or an int32 device
+    tensor the caller has already checked.
+    Where gemm_plan_sets refuses the shape (rows_per_img % 64 != 0: latents under 8x8) the call runs linear_masked
+    once per maximal run of consecutive images sharing a set, on row slices of x / residual / out and a contiguous
+    copy of the run's keep columns; that path needs the host form of image_set."""
+    lib = _lib.load()
+    xp, lda = _rows(x, "x")
+    M, K = x.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise ValueError(f"linear_masked_sets: weight {tuple(w.shape)} does not match input K={K}")
+    if rows_per_img <= 0 or M % rows_per_img:
+        raise ValueError(f"linear_masked_sets: {M} rows are not whole images of {rows_per_img}")
+    nimg = M // rows_per_img
+    if wmasks.dim() != 3 or tuple(wmasks.shape[1:]) != (K // 64, N) or wmasks.dtype != torch.int64:
+        raise ValueError(f"wmasks must be int64 [nsets, {K // 64}, {N}], got {wmasks.dtype} {tuple(wmasks.shape)}")
+    nsets = wmasks.shape[0]
+    if keep is not None and (tuple(keep.shape) != (K // 64, M) or keep.dtype != torch.int64):
+        raise ValueError(f"keep must be int64 [{K // 64}, {M}], got {keep.dtype} {tuple(keep.shape)}")
+    host_ids = None
+    if not isinstance(image_set, torch.Tensor):
+        host_ids = [int(s) for s in image_set]
+        if len(host_ids) != nimg or any(s < 0 or s >= nsets for s in host_ids):
+            raise ValueError(f"image_set must hold {nimg} set ids in [0, {nsets}), got {host_ids}")
+    elif image_set.dtype != torch.int32 or tuple(image_set.shape) != (nimg,):
+        raise ValueError(f"image_set must be int32 [{nimg}], got {image_set.dtype} {tuple(image_set.shape)}")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
+    op, ldc = _rows(out, "out")
+    rp, ldr = (None, 0) if residual is None else _rows(residual, "residual")
+    plan = (ctypes.c_int * 5)()
+    st = lib.sdmoe_gemm_plan_sets(int(keep is not None), M, N, K, rows_per_img, int(residual is not None), WS_FLOATS,
+                                  plan)
+    if st == -3:  # a tile would straddle two images: one launch per run of images on one set
+        if host_ids is None:
+            raise _lib.SdmoeError(f"linear_masked_sets: rows_per_img = {rows_per_img} runs per image run, which needs "
+                                  "image_set as a host sequence")
+        for i0, i1, s in image_set_runs(host_ids):
+            r0, r1 = i0 * rows_per_img, i1 * rows_per_img
+            linear_masked(x[r0:r1], w, bias, keep=None if keep is None else keep[:, r0:r1].contiguous(),
+                          wmask=wmasks[s], residual=None if residual is None else residual[r0:r1], out=out[r0:r1])
+        return out
+    _lib.check(st, "sdmoe_gemm_plan_sets")
+    if host_ids is None:
+        ids = image_set
+    elif image_set_dev is not None:
+        ids = image_set_dev
+        if ids.dtype != torch.int32 or tuple(ids.shape) != (nimg,):
+            raise ValueError(f"image_set_dev must be int32 [{nimg}], got {ids.dtype} {tuple(ids.shape)}")
+    else:
+        ids = torch.tensor(host_ids, dtype=torch.int32, device=x.device)
+    ws = _workspace(x.device)
+    st = lib.sdmoe_linear_masked_sets(xp, lda, None if keep is None else _dev(keep, "keep", torch.int64), _dev(w, "w"),
+                                      w.stride(0), _dev(wmasks, "wmasks", torch.int64), wmasks.stride(0),
+                                      _dev(ids, "image_set", torch.int32), nsets, rows_per_img, _ptr(bias), rp, ldr,
+                                      op, ldc, M, N, K, ws.data_ptr(), ws.numel(), _stream())
+    _lib.check(st, "sdmoe_linear_masked_sets")
+    return out
+
+
 def linear(x, w, bias=None, *, out=None, residual=None, act=ACT_NONE, coladd=None, coladd_bstride=0,
            rows_per_batch=0, gn=None, wmask=None, wmask_bits=None):
     """out = act(GN?(x) @ w.T + bias + coladd) + residual.  w: [N, K] fp16 (nn.Linear layout).

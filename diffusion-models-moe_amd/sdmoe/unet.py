@@ -357,7 +357,9 @@ class FeedForward(nn.Module):
             keep = geglu._out_keep
             keep = keep[0] if keep is not None and keep[1] == h2.data_ptr() else None
             if masker is not None:
-                return masker.fused_linear(down, h2, keep, perm[0].perm_dev, wp, residual)
+                # (a receiver whose mask differs per image, WandaRemovePerPrompt, asks for the call's image count)
+                kw = {"nimg": nimg} if getattr(masker, "_sdmoe_fused_nimg", False) else {}
+                return masker.fused_linear(down, h2, keep, perm[0].perm_dev, wp, residual, **kw)
             if keep is not None:
                 return ops.linear_keep(h2, keep, wp, down.bias, residual=residual)
             return ops.linear(h2, wp, down.bias, residual=residual)

@@ -234,6 +234,46 @@ int sdmoe_linear_masked(const void* A, long lda, const void* keep, const void* W
                         float* workspace, long workspace_floats, void* stream);
 
 /*
+ * sdmoe_linear_masked_sets — sdmoe_linear_masked with one Wanda mask per image of the call:
+ *   C[m] = (A[m] ⊙ keep[m]) @ (W ⊙ (1 - Mask[image_set[m / rows_per_img]]))^T + bias + R[m].
+ *   wmasks: nsets masks in sdmoe_wmask_kmajor's layout ([K/64][N] 64-bit words each), set s at wmasks + s * set_stride
+ *     words (set_stride >= K/64 * N); an all-zero set is the unmasked product;
+ *   image_set: device int32 [M / rows_per_img], 0 <= image_set[i] < nsets (the caller's guarantee: the kernel does
+ *     not range-check it); keep nullable as in sdmoe_linear_masked. M % rows_per_img == 0.
+ * One launch at the full grid: every row tile reads its image's set id (one scalar load per workgroup) and stages its
+ * mask bytes from that set. No tile straddles two images: the launch is sdmoe_linear_masked's own plan where that
+ * tile's rows divide rows_per_img -- then a uniform image_set gives sdmoe_linear_masked's bits -- else a 64-row tile
+ * with the split-K policy applied to that tile (SD-1.4 / SDXL: only the mid block, rows_per_img = 64); SDMOE_EUNSUP
+ * when rows_per_img % 64 != 0 (the caller then runs sdmoe_linear_masked per run of images, sdmoe/ops.py).
+ * Replaces: the one-prompt-per-call loop of benchmarks/unified_editing.py:106-126, where every prompt goes through
+ * MultiConceptRemoverWanda.remove_concepts (neuron_receivers/multi_concept_remover.py:55-99) with its own concept
+ * list, i.e. its own F.linear(input[0], W.clone() * (1 - M[t][l]), b) (remove_wanda_neurons_fast.py:69-83).
+ */
+int sdmoe_linear_masked_sets(const void* A, long lda, const void* keep, const void* W, long ldw, const void* wmasks,
+                             long set_stride, const int* image_set, int nsets, int rows_per_img, const void* bias,
+                             const void* R, long ldr, void* C, long ldc, int M, int N, int K, float* workspace,
+                             long workspace_floats, void* stream);
+
+/*
+ * sdmoe_gemm_plan_sets — sdmoe_gemm_plan for sdmoe_linear_masked_sets (has_keep: with the A keep bits): out[0..4] as
+ * there; out[0] divides rows_per_img. SDMOE_EUNSUP exactly where the launch would refuse (rows_per_img % 64 != 0 and
+ * the shape's own tile does not divide it).
+ */
+int sdmoe_gemm_plan_sets(int has_keep, int M, int N, int K, int rows_per_img, int has_residual, long workspace_floats,
+                         int* out);
+
+/*
+ * sdmoe_wmask_union_sets — the masks of sdmoe_linear_masked_sets from per-concept masks, one streaming launch for all
+ * sets of a (t, l): out[s * words + w] = OR over the concepts c with bit c of select[s] set of
+ * masks[c * mask_stride + w] (64-bit words; select: device uint32 [nsets], nconcepts <= 32, bits past nconcepts
+ * ignored; mask_stride >= words). select[s] == 0 gives the all-zero (unmasked) set.
+ * Replaces: MultiConceptRemoverWanda.handle_multiple_concepts (multi_concept_remover.py:43-53), the host-side
+ * element-wise OR over every (t, l) mask per request -- here exactly the listed concepts, per prompt, on the device.
+ */
+int sdmoe_wmask_union_sets(const void* masks, long mask_stride, int nconcepts, const unsigned* select, int nsets,
+                           long words, void* out, void* stream);
+
+/*
  * sdmoe_gemm_plan — query (no device memory, no launch): the launch sdmoe_linear (mode 0), sdmoe_linear_masked
  * with keep (4), wmask (5) or both (6), or sdmoe_linear_ln (7) would make for an M x N x K product with / without a
  * residual and activation act, given workspace_floats of split-K workspace (0 = none), or sdmoe_linear_geglu (3; 15 =
