@@ -1893,7 +1893,16 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(const half_t* __restrict__
 }
 
 // GroupNorm fold (sdmoe_gn_fold): one wave per (image, output row n): Wf[i][n, k] = fp16(W[n, k] * scale[i, k]) and
-// colbias[i][n] = bias[n] + sum_k W[n, k] * shift[i, k] (fp32, fixed-order lane sums + xor tree: deterministic)
+// colbias[i][n] = bias[n] + sum_k float(Wf[i][n, k]) * (shift[i, k] / scale[i, k]) (fp32, fixed-order lane sums + xor
+// tree: deterministic). The bias is taken from the ROUNDED weights so that the GEMM computes sum_k Wf * (x + shift /
+// scale) with -shift / scale = mean - beta std / gamma, a centre within about one std of the group mean: the fp16
+// rounding of Wf then multiplies a centred value. (From the unrounded W -- sum_k W * shift -- the rounding was
+// multiplied by the activation's mean with nothing to cancel it: 1.3e-2 relative L2 at a group |mean| / std of 64.)
+// Where |scale| < GN_FOLD_MIN_SCALE (scale == 0 above all: a zero gamma) Wf is 0 or an fp16 subnormal, there is
+// nothing worth cancelling, shift / scale has no meaning, and the term is W[n, k] * shift[i, k].
+// The ratio is one v_rcp_f32 (1 ulp) and a multiply per element; it costs this kernel 3-5 % (DESIGN.md section 4,
+// where the mappings that share the ratio between rows are measured too: all slower).
+constexpr float GN_FOLD_MIN_SCALE = 6.103515625e-05f;  // 2^-14, the smallest normal fp16
 __global__ __launch_bounds__(256) void gn_fold_kernel(const half_t* __restrict__ W, long ldw, int N, int K,
                                                       const half_t* __restrict__ bias, const float* __restrict__ scale,
                                                       const float* __restrict__ shift, half_t* __restrict__ Wf,
@@ -1913,11 +1922,19 @@ __global__ __launch_bounds__(256) void gn_fold_kernel(const half_t* __restrict__
     const float h[8] = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
     half8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      o[j] = (half_t)((float)w[j] * s[j]);
-      acc = __builtin_fmaf((float)w[j], h[j], acc);
-    }
+    for (int j = 0; j < 8; ++j) o[j] = (half_t)((float)w[j] * s[j]);
+    // The bias must be taken from the very bits that are stored. Left free, the compiler forms the product twice,
+    // once fused into the fp16 conversion (v_fma_mixlo_f16) and once as multiply + v_cvt_pk_f16_f32, and the two
+    // differ in the last bit for some elements: one ulp of a |Wf| of 16 times a ratio of 2 put the bias 1.6e-2 off
+    // the stored weights on a constant group.
+    asm volatile("" : "+v"(o));
     *reinterpret_cast<half8*>(wo + k) = o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool centred = __builtin_fabsf(s[j]) >= GN_FOLD_MIN_SCALE;
+      acc = __builtin_fmaf(centred ? (float)o[j] : (float)w[j], centred ? h[j] * __builtin_amdgcn_rcpf(s[j]) : h[j],
+                           acc);
+    }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);

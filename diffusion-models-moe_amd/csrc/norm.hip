@@ -30,8 +30,22 @@ int gn_chunk_width(int C, int groups) {
   return (wc <= 256 && wc / cpg <= 32 && C % wc == 0) ? wc : 0;
 }
 
+// Reference of the shifted sums of one (image, group); g0 = the group's first channel in the image's row 0. The sums
+// are well conditioned while |ref - mean| is a few std: the variance b / n - m1^2 cancels ((ref - mean) / std)^2 of its
+// leading digits. ref is the mean of 8 channels spread over the group in row 0 (the first among them), rounded to fp16
+// so that x - ref stays exact. A single element as the reference put the whole cancellation on that element: an
+// outlier there (|ref - mean| / std = sqrt(n), n the group's element count) cost n * 4e-8 of the variance, 4e-3 at
+// 1088 rows x 80 channels; with 8 samples the same outlier costs 64 times less. Every statistics kernel and the
+// finalize call this, so their sums stay bit-identical.
+SDMOE_DEV float gn_ref(const half_t* g0, int cpg) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s += (float)g0[(j * cpg) >> 3];
+  return (float)(half_t)(s * 0.125f);
+}
+
 // Partial sums of (x - ref) and (x - ref)^2 over a slice of rows of one image, for every group at once.
-// ref = first element of the group in the image's row 0 (shifted sums keep the variance well conditioned).
+// ref = gn_ref of the group (shifted sums keep the variance well conditioned).
 // Reads whole rows with 16-B loads: "virtual thread" vt (NV per thread) owns 8-channel chunk vt % nch and row
 // phase vt / nch, accumulates per-channel sums in registers; LDS reduces phases, then channels per group.
 SDMOE_DEV void gn_accum8(const half8& v, const float (&rf)[8], float (&s1)[8], float (&s2)[8]) {
@@ -54,7 +68,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const half_t* __restric
   const int RP = max(1, (256 * NV) / nch);
   const int r0 = (int)((long)HW * s / S), r1 = (int)((long)HW * (s + 1) / S);
   const half_t* base = X + (long)img * HW * ldx;
-  if (tid < G) refs[tid] = (float)base[tid * cpg];
+  if (tid < G) refs[tid] = gn_ref(base + tid * cpg, cpg);
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
@@ -118,7 +132,7 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const half_t* __restrict_
   const int chunk = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
   const int cpg = C / G, c0 = chunk * WC, nq = WC / 8, R = 256 / nq, gc = WC / cpg;
   const half_t* base = X + (long)img * HW * ldx + c0;
-  if (tid < gc) refs[tid] = (float)base[tid * cpg];
+  if (tid < gc) refs[tid] = gn_ref(base + tid * cpg, cpg);
   __syncthreads();
   const int q = tid % nq, ph = tid / nq;
   float rf[8], s1[8], s2[8];
@@ -193,7 +207,7 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const half_t* __restrict_
   const int chunk = blockIdx.x % nchunk, slice = blockIdx.x / nchunk, img = blockIdx.y, tid = threadIdx.x;
   const int cpg = C / G, c0 = chunk * WC, nq = WC / 8, R = 256 / nq, gc = WC / cpg;
   const half_t* base = X + (long)img * HW * ldx + c0;
-  if (tid < gc) refs[tid] = (float)base[tid * cpg];
+  if (tid < gc) refs[tid] = gn_ref(base + tid * cpg, cpg);
   __syncthreads();
   const int q = tid % nq, ph = tid / nq;
   float rf[8], s1[8], s2[8];
@@ -303,7 +317,7 @@ __global__ __launch_bounds__(256) void gn_fused_reg_kernel(const half_t* __restr
   }
   const half8 gm8 = *reinterpret_cast<const half8*>(gamma + c0 + q * 8);
   const half8 bt8 = *reinterpret_cast<const half8*>(beta + c0 + q * 8);
-  if (tid < gc) refs[tid] = (float)base[tid * cpg];
+  if (tid < gc) refs[tid] = gn_ref(base + tid * cpg, cpg);
   __syncthreads();
   float rf[8], s1[8], s2[8];
 #pragma unroll
@@ -383,7 +397,7 @@ __global__ __launch_bounds__(64) void gn_finalize_kernel(const half_t* __restric
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
   const double n = (double)HW * cpg;
-  const double ref = (double)(float)X[(long)img * HW * ldx + g * cpg];
+  const double ref = (double)gn_ref(X + (long)img * HW * ldx + g * cpg, cpg);
   const double m1 = a / n;
   double var = b / n - m1 * m1;
   if (var < 0) var = 0;

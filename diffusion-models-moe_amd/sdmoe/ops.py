@@ -499,7 +499,9 @@ def groupnorm(x, nimg, HW, gamma, beta, eps, groups=32, silu=False, out=None):
 def gn_fold(w, bias, scale, shift):
     """Per-image GroupNorm-folded weights of a linear (sdmoe_gn_fold): Wf [nimg, N, K] fp16 and colbias [nimg, N]
     fp32 with x . Wf[i]^T + colbias[i] = GN(x) . w^T + bias on the rows of image i (scale / shift from
-    groupnorm_stats)."""
+    groupnorm_stats). Wf[i] = fp16(w * scale[i]) and colbias[i] = bias + Wf[i] . (shift[i] / scale[i]), the bias taken
+    from the rounded weights (w * shift where |scale| < 2^-14, e.g. gamma == 0): the rounding of Wf then multiplies x + shift / scale, an
+    activation centred on its group, and the fold holds the accuracy of groupnorm + linear at any group offset."""
     lib = _lib.load()
     N, K = w.shape
     nimg = scale.shape[0]

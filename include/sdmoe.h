@@ -116,8 +116,12 @@ int sdmoe_groupnorm(const void* X, long ldx, int nimg, int HW, int C, int groups
  * GroupNorm folded into the linear (1x1 conv) that consumes it — Transformer2DModel.norm -> proj_in (diffusers,
  * external): the normalised activation is never written or re-read.
  *  sdmoe_gn_fold (per call, after sdmoe_groupnorm_stats): for each image i, Wf[i][n, k] = fp16(W[n, k] * scale[i, k])
- *    (Wf [nimg][N][K], dense) and colbias[i][n] = bias[n] + sum_k W[n, k] * shift[i, k] (fp32 [nimg][N]; bias may
- *    be NULL), so proj_in(GN(x)) = x . Wf[i]^T + colbias[i] on the rows of image i. K % 8 == 0, ldw % 8 == 0.
+ *    (Wf [nimg][N][K], dense) and colbias[i][n] = bias[n] + sum_k float(Wf[i][n, k]) * (shift[i, k] / scale[i, k])
+ *    (fp32 [nimg][N]; bias may be NULL; the term is W[n, k] * shift[i, k] where |scale[i, k]| < 2^-14, e.g. gamma == 0),
+ *    so proj_in(GN(x)) = x . Wf[i]^T + colbias[i] on the rows of image i. The bias comes from the ROUNDED weights:
+ *    the GEMM then computes sum_k Wf (x + shift / scale), the fp16 rounding of Wf multiplies an activation centred to
+ *    within about one std of its group mean, and the fold is as accurate as GroupNorm + linear whatever the group's
+ *    |mean| / std (from the unrounded W it left the suite's bar at |mean| / std ~ 16). K % 8 == 0, ldw % 8 == 0.
  *  sdmoe_linear_per_image: C[m, n] = sum_k A[m, k] Wf[m / rows_per_batch][n, k] + colbias[m / rows_per_batch][n]
  *    + R[m, n] (weights of image i at Wf + i * w_bstride elements, row stride ldw; colbias row stride
  *    colbias_bstride). rows_per_batch % 256 == 0 (no GEMM tile straddles two images), K % 64 == 0, N % 8 == 0.

@@ -171,7 +171,10 @@ def test_gn_fold_proj_in(nimg, HW, C, N, mean):
     close(out, ref)
     # the folded weights and bias themselves
     close(wf.float(), w.float()[None] * sc[:, None, :], rel=1e-3)
-    close(cb, b.float()[None] + sh @ w.float().t(), tol=1e-4, rel=1e-5)
+    # (the bias is taken from the ROUNDED weights, b + Wf . (shift / scale), w * shift where |scale| < 2^-14; fp64)
+    terms = torch.where((sc.abs() >= 2.0 ** -14)[:, None, :], wf.double() * (sh.double() / sc.double())[:, None, :],
+                        w.double()[None] * sh.double()[:, None, :])
+    close(cb.double(), b.double()[None] + terms.sum(-1), tol=1e-4, rel=1e-5)
     # with a residual, and the unfused path it replaces agrees to fp16 rounding
     r = rnd(nimg * HW, N, seed=55)
     close(ops.linear_per_image(x, wf, cb, HW, residual=r), ref + r.float())
