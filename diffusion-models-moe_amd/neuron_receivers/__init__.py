@@ -1,12 +1,15 @@
 """Drop-in receiver API of the reference's `neuron_receivers` package.
 
 Importing this package requires the sdmoe HIP library at call time (no CPU path). Hot-path receivers (MOEFy,
-RemoveExperts, WandaRemoveNeuronsFast, WandaRemovePerPrompt, MultiConceptRemoverWanda) plus the two discovery receivers that produce
-their inputs (GetExperts -> expert lists, Wanda -> column norms -> masks). The remaining
+RemoveExperts, RemoveNeurons, WandaRemoveNeuronsFast, WandaRemovePerPrompt, MultiConceptRemoverWanda) plus the discovery
+receivers that produce their inputs (GetExperts -> expert lists, Wanda -> column norms -> masks, NeuronPredictivity /
+NeuronPredictivityBB -> max-activation statistics -> paired t-test or AP neuron masks). The remaining
 statistics/HPO receivers of the reference are not exported.
 """
 from neuron_receivers.base_receiver import BaseNeuronReceiver, GEGLU, GELU  # noqa: F401
 from neuron_receivers.predictivity import NeuronPredictivity  # noqa: F401
+from neuron_receivers.neuron_predictivity_bb import NeuronPredictivityBB  # noqa: F401
+from neuron_receivers.remove_skilled_neurons import RemoveNeurons  # noqa: F401
 from neuron_receivers.moefy import MOEFy  # noqa: F401
 from neuron_receivers.remove_skilled_experts import RemoveExperts  # noqa: F401
 from neuron_receivers.remove_wanda_neurons_fast import WandaRemoveNeuronsFast  # noqa: F401

@@ -11,6 +11,11 @@ masks the hot-path receivers consume.
   * update_set_diff / select_skilled_experts / save_expert_lists — the host bookkeeping of
     modularity/moefy_skilled_experts.py:97-124 and mod_utils.py:178-182 that turns GetExperts label lists into
     the timestep_{t}_layer_{l}.json files RemoveExperts reads.
+  * Average / StandardDev / StatMeter — the running per-neuron statistics of NeuronPredictivity (utils.py:233-317):
+    host-side numpy on the fp16 maxima the receivers copy back once per pipeline call, one numpy operation per
+    step so every intermediate is rounded to fp16 exactly where the reference's is.
+  * t_test_neurons / ap_neurons / save_neuron_masks — modularity/paired_t_test.py:66-79,142 and
+    modularity/skilled_neuron_ap.py:166-177: statistics -> the predictivity_{t}_{l}.json 0/1 masks RemoveNeurons reads.
 """
 from __future__ import annotations
 
@@ -126,3 +131,95 @@ def save_expert_lists(lists, path):
         for l, ids in layers.items():
             with open(os.path.join(path, f"timestep_{t}_layer_{l}.json"), "w") as f:
                 json.dump([int(e) for e in ids], f)
+
+
+class Average:
+    """Running mean: sum += val, avg = sum / count (in the dtype of val: fp16 rows give fp16 sums)."""
+
+    def __init__(self):
+        self.val = 0
+        self.sum = 0
+        self.count = 0
+        self.avg = 0
+
+    def update(self, val, n=1):
+        self.val = val
+        self.sum = self.sum + val * n
+        self.count += n
+        self.avg = self.sum / self.count
+
+
+class StandardDev:
+    """Welford's running variance: n, mean and M2 (the sum of squared deviations), element-wise in the dtype of x."""
+
+    def __init__(self):
+        self.n = 0
+        self.mean = 0
+        self.M2 = 0
+
+    def update(self, x):
+        self.n += 1
+        delta = x - self.mean
+        self.mean = self.mean + delta / self.n
+        self.M2 = self.M2 + delta * (x - self.mean)
+
+    def variance(self):
+        return float("nan") if self.n < 2 else self.M2 / (self.n - 1)
+
+    def stddev(self):
+        return self.variance() ** 0.5
+
+
+class StatMeter:
+    """An Average and a StandardDev per (timestep, layer); save() writes the reference's predictivity JSON."""
+
+    def __init__(self, T, n_layers):
+        self.T = T
+        self.n_layers = n_layers
+        self.results = {"time_steps": {t: {l: {"avg": Average(), "std": StandardDev()} for l in range(n_layers)}
+                                       for t in range(T)}}
+
+    def update(self, val, t, n_layer):
+        cell = self.results["time_steps"][t][n_layer]
+        cell["avg"].update(val)
+        cell["std"].update(val)
+
+    def to_json(self):
+        """{"time_steps": {t: {l: {"avg": [...], "std": [...]}}}} (a cell never updated: avg 0, std NaN)."""
+        def plain(v):
+            return v.tolist() if isinstance(v, np.ndarray) else v
+        return {"time_steps": {t: {l: {"avg": plain(c["avg"].avg), "std": plain(c["std"].stddev())}
+                                   for l, c in layers.items()} for t, layers in self.results["time_steps"].items()}}
+
+    def save(self, path):
+        with open(path, "w") as f:
+            json.dump(self.to_json(), f)
+
+
+def t_test_neurons(base_avg, adj_avg, diff_std, n_prompts, critical_value):
+    """Paired t-test of one (t, l) (modularity/paired_t_test.py:72-79,142): t = (base - adj) / (diff_std /
+    sqrt(n_prompts)) in float64; returns (t, t < -critical_value) -- neurons that fire more on the concept prompts."""
+    base = np.asarray(base_avg, dtype=np.float64)
+    adj = np.asarray(adj_avg, dtype=np.float64)
+    diff = np.asarray(diff_std, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = (base - adj) / (diff / (n_prompts ** 0.5))
+    return t, t < -critical_value
+
+
+def ap_neurons(hit_rate, ratio=0.05):
+    """modularity/skilled_neuron_ap.py:166-172: the int(ratio * F) best-ranked neurons of argsort()[::-1] as a 0/1
+    float mask."""
+    pred = np.asarray(hit_rate)
+    mask = np.zeros(len(pred))
+    mask[pred.argsort()[::-1][:int(ratio * len(pred))]] = 1
+    return mask
+
+
+def save_neuron_masks(masks, path):
+    """predictivity_{t}_{l}.json files (lists of 0.0 / 1.0) for RemoveNeurons; masks[t][l]: 0/1 (or bool) [F]."""
+    os.makedirs(path, exist_ok=True)
+    for t, layers in masks.items():
+        for l, m in layers.items():
+            with open(os.path.join(path, f"predictivity_{t}_{l}.json"), "w") as f:
+                json.dump([float(v) for v in np.asarray(m).reshape(-1) != 0], f)

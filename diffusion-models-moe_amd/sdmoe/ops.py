@@ -831,6 +831,79 @@ def geglu_route(y, routing: Routing | None, act=ACT_GELU, removed=None, out=None
     return out
 
 
+def neuron_bits(mask01, device) -> torch.Tensor:
+    """A 0/1 list of length F (F % 32 == 0) packed into [F/32] int32 words, bit n % 32 of word n // 32 = neuron n
+    (little-endian within a word): the override_bits of geglu_neurons."""
+    import numpy as np
+    m = np.asarray(mask01).reshape(-1) != 0
+    if m.size % 32:
+        raise ValueError(f"neuron_bits: {m.size} neurons are not a multiple of 32")
+    words = np.packbits(m, bitorder="little").view("<u4").astype(np.uint32).view(np.int32)
+    return torch.from_numpy(words.copy()).to(device)
+
+
+def position_bits(positions, rows_per_img: int, device) -> torch.Tensor:
+    """Token positions (each in [0, rows_per_img)) as the [ceil(rows_per_img / 32)] int32 pos_bits of geglu_neurons."""
+    import numpy as np
+    m = np.zeros(-(-int(rows_per_img) // 32) * 32, dtype=bool)
+    idx = np.asarray(list(positions), dtype=np.int64)
+    if idx.size == 0 or idx.min() < 0 or idx.max() >= rows_per_img:
+        raise ValueError(f"position_bits: positions must be a non-empty subset of [0, {rows_per_img})")
+    m[idx] = True
+    words = np.packbits(m, bitorder="little").view("<u4").astype(np.uint32).view(np.int32)
+    return torch.from_numpy(words.copy()).to(device)
+
+
+def geglu_neurons(y, act=ACT_GELU, *, override_bits=None, override_value=0.0, gate_out=None, rows_per_img=0,
+                  img_group=None, ngroups=1, pos_bits=None, colmax=None, out=None, workspace=None):
+    """Dense GEGLU over y = proj(x) [M, 2F] with a per-neuron gate override and a per-group column maximum
+    (sdmoe_geglu_neurons): out = value * g', g' = fp16(override_value) where override_bits (int32 [F/32], neuron_bits)
+    is set, else g = act(gate); gate_out (optional [M, F]) receives g'; colmax (optional fp16 [ngroups, F]) the
+    maximum of g -- before the override -- over the rows of the images of each group (image i = rows_per_img rows,
+    group img_group[i], int32 device [M / rows_per_img]; None = all group 0), restricted to the positions of pos_bits
+    (int32 [ceil(rows_per_img / 32)], position_bits) when given. workspace: fp32 scratch for the per-slab partial
+    maxima (default: the device's shared workspace). Returns out."""
+    lib = _lib.load()
+    if act == ACT_GELU:
+        ensure_gelu_table(y.device)
+    yp, ldy = _rows(y, "y")
+    M = y.shape[0]
+    F = y.shape[1] // 2
+    if out is None:
+        out = torch.empty((M, F), dtype=torch.float16, device=y.device)
+    op, ldo = _rows(out, "out")
+    if tuple(out.shape) != (M, F):
+        raise ValueError(f"geglu_neurons: out {tuple(out.shape)} is not {(M, F)}")
+    gp, ldg = (None, 0) if gate_out is None else _rows(gate_out, "gate_out")
+    if gate_out is not None and tuple(gate_out.shape) != (M, F):
+        raise ValueError(f"geglu_neurons: gate_out {tuple(gate_out.shape)} is not {(M, F)}")
+    rpi = int(rows_per_img)
+    nimg = M // rpi if rpi > 0 and M % rpi == 0 else 1
+    obp = None
+    if override_bits is not None:
+        if override_bits.numel() * 32 != F:
+            raise ValueError(f"geglu_neurons: {override_bits.numel()} override words for F={F}")
+        obp = _dev(override_bits, "override_bits", torch.int32)
+    cp = igp = pbp = None
+    if colmax is not None:
+        if tuple(colmax.shape) != (int(ngroups), F):
+            raise ValueError(f"geglu_neurons: colmax {tuple(colmax.shape)} is not {(int(ngroups), F)}")
+        cp = _dev(colmax, "colmax")
+        if img_group is not None:
+            if (rpi <= 0 or M % rpi == 0) and img_group.numel() != nimg:
+                raise ValueError(f"geglu_neurons: img_group has {img_group.numel()} entries for {nimg} images")
+            igp = _dev(img_group, "img_group", torch.int32)
+        if pos_bits is not None:
+            if pos_bits.numel() != -(-(rpi if rpi > 0 else M) // 32):
+                raise ValueError(f"geglu_neurons: {pos_bits.numel()} pos_bits words for {rpi if rpi > 0 else M} rows")
+            pbp = _dev(pos_bits, "pos_bits", torch.int32)
+    ws = _workspace(y.device) if workspace is None else workspace
+    st = lib.sdmoe_geglu_neurons(yp, ldy, M, F, act, obp, float(override_value), op, ldo, gp, ldg, rpi, igp,
+                                 int(ngroups), pbp, cp, _dev(ws, "workspace", torch.float32), ws.numel(), _stream())
+    _lib.check(st, "sdmoe_geglu_neurons")
+    return out
+
+
 def expert_mean_topk(score, k: int, rows_per_img: int = 0, row_idx=None, mean_out=None, topk_out=None):
     """GetExperts statistic (get_experts.py:72-80): mean of the fp16 expert scores [M, E] over all tokens, or
     over positions row_idx (int32 device tensor) of every rows_per_img-row image, then the top-k expert ids

@@ -277,6 +277,29 @@ class GEGLU(nn.Module):
             out = ops.geglu_route(self.proj.run(x2), None, act)
         return out.view(*shp[:-1], self.inner_dim)
 
+    def neurons(self, x, override_bits=None, override_value=0.0, want_gate=False, colmax=None, img_group=None,
+                ngroups=1, pos_bits=None):
+        """proj GEMM + the neuron-level streaming pass (ops.geglu_neurons), ignoring any MoE routing: value * g' in the
+        natural neuron order, g' = act(gate) with the neurons of override_bits set to override_value
+        (RemoveNeurons, neuron_receivers/remove_skilled_neurons.py:26-42); colmax ([ngroups, 4C] fp16, optional)
+        receives the per-group maximum of act(gate) over the tokens (pos_bits: only those positions) of the images
+        x[i] of each group (NeuronPredictivity, predictivity.py:42-53). x: [images, tokens, C] (or [tokens, C]: one
+        image). Returns (out, g' or None)."""
+        shp = x.shape
+        x2 = x.reshape(-1, shp[-1])
+        norm = self._take_ln(x)
+        if norm is not None:
+            x2 = ops.layernorm(x2, norm.weight, norm.bias, norm.eps)
+        self._out_perm = None
+        self._out_keep = None
+        y = self.proj.run(x2)
+        gate = torch.empty((x2.shape[0], self.inner_dim), dtype=torch.float16, device=x.device) if want_gate else None
+        out = ops.geglu_neurons(y, act_code(self.gelu), override_bits=override_bits, override_value=override_value,
+                                gate_out=gate, rows_per_img=shp[-2] if x.dim() >= 3 else 0, img_group=img_group,
+                                ngroups=ngroups, pos_bits=pos_bits, colmax=colmax)
+        out = out.view(*shp[:-1], self.inner_dim)
+        return out, (gate.view(*shp[:-1], self.inner_dim) if want_gate else None)
+
     def forward(self, x, scale=1.0):
         if self._sdmoe_deferred and self._forward_hooks:
             return None  # a sdmoe receiver hook computes the routed output (no double compute)

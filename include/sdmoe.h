@@ -333,6 +333,28 @@ int sdmoe_wanda_mask(const void* W, long ldw, int C, int F, const void* norm_bas
                      void* bits, void* stream);
 
 /*
+ * sdmoe_geglu_neurons — the neuron-level path: NeuronPredictivity / NeuronPredictivityBB.hook_fn
+ * (neuron_receivers/predictivity.py:42-53, neuron_predictivity_bb.py:43-63) and RemoveNeurons.hook_fn
+ * (neuron_receivers/remove_skilled_neurons.py:26-42) as one streaming pass over Y = proj(x) = [value | gate]
+ * [M, 2F] (row stride ldy):
+ *   g   = fp16(act(gate))                  the activation of sdmoe_geglu_route (the registered GELU table, else erf)
+ *   g'  = override bit n set ? fp16(override_value) : g      override_bits [F/32] words, bit n % 32 of word n / 32;
+ *                                                            NULL = no override
+ *   out = fp16(float(value) * float(g'))   [M, F] (ldo); gate_out (nullable, ldg) = g'
+ *   colmax (nullable, fp16 [ngroups, F]): colmax[img_group[i]][n] = max of g (BEFORE the override) over the rows of
+ *     image i = rows [i * rows_per_img, (i + 1) * rows_per_img) whose position has its bit set in pos_bits
+ *     [ceil(rows_per_img / 32)] (NULL = every position); img_group NULL = every image in group 0; rows_per_img 0 =
+ *     one image of M rows. A group without a selected row gets -inf. No atomics: deterministic.
+ * With override_bits == NULL and colmax == NULL, out is bit-identical to sdmoe_geglu_route(E = 0).
+ * F % 32 == 0, ldy % 8 == 0 (SDMOE_ESHAPE); M % rows_per_img == 0 (SDMOE_EARG).
+ * workspace (used for colmax only) >= (M / rows_per_img) * ceil(rows_per_img / 64) * F / 2 floats.
+ */
+int sdmoe_geglu_neurons(const void* Y, long ldy, int M, int F, int act, const unsigned* override_bits,
+                        float override_value, void* out, long ldo, void* gate_out, long ldg, int rows_per_img,
+                        const int* img_group, int ngroups, const unsigned* pos_bits, void* colmax, float* workspace,
+                        long workspace_floats, void* stream);
+
+/*
  * Offline MoE-fication: ParamSplit.split (moefication/moe_utils.py:97-107) clusters the
  * L2-normalised gate rows of each GEGLU with KMeansConstrained(size_min = size_max = expert_size).
  * sdmoe_sqdist_f32 — D[i][c] = max(|x_i|^2 + |c_c|^2 - 2 x_i.c_c, 0), fp32 device arrays (exact fp32 MFMA
