@@ -3,8 +3,10 @@
 Importing this package requires the sdmoe HIP library at call time (no CPU path). Hot-path receivers (MOEFy,
 RemoveExperts, RemoveNeurons, WandaRemoveNeuronsFast, WandaRemovePerPrompt, MultiConceptRemoverWanda) plus the discovery
 receivers that produce their inputs (GetExperts -> expert lists, Wanda -> column norms -> masks, NeuronPredictivity /
-NeuronPredictivityBB -> max-activation statistics -> paired t-test or AP neuron masks). The remaining
-statistics/HPO receivers of the reference are not exported.
+NeuronPredictivityBB -> max-activation statistics -> paired t-test or AP neuron masks; ExpertPredictivity -> per-expert
+maximum routing scores -> paired t-test -> expert lists) and FrequencyMeasure, the per-expert
+selection histogram for choosing topk_experts. The remaining receivers of the reference (AddExperts, SparsityMeasure,
+SaveStates and the HPO receivers) are not exported.
 """
 from neuron_receivers.base_receiver import BaseNeuronReceiver, GEGLU, GELU  # noqa: F401
 from neuron_receivers.predictivity import NeuronPredictivity  # noqa: F401
@@ -16,4 +18,6 @@ from neuron_receivers.remove_wanda_neurons_fast import WandaRemoveNeuronsFast  #
 from neuron_receivers.remove_wanda_per_prompt import WandaRemovePerPrompt  # noqa: F401
 from neuron_receivers.multi_concept_remover import MultiConceptRemoverWanda  # noqa: F401
 from neuron_receivers.get_experts import GetExperts  # noqa: F401
+from neuron_receivers.expert_activation import ExpertPredictivity  # noqa: F401
+from neuron_receivers.frequency_measure import FrequencyMeasure  # noqa: F401
 from neuron_receivers.wanda_receiver import Wanda  # noqa: F401

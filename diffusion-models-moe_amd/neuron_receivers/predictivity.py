@@ -38,6 +38,7 @@ class NeuronPredictivity(BaseNeuronReceiver):
         self._pending = []      # (t, l, device [ngroups, F] maxima) of the running pipeline call
         self._nprompts = None   # None: a single prompt (one group); B: a list of B prompts
         self._img_tables = {}       # (image count, device) -> int32 device image -> prompt table
+        self.flush_count = 0        # device->host copies done by flush() (one per pipeline call)
 
     # ---- statistics, built on first use ----------------------------------------------------------------------------
     @property
@@ -121,6 +122,7 @@ class NeuronPredictivity(BaseNeuronReceiver):
             return
         pending, self._pending = self._pending, []
         flat = torch.cat([p[2].reshape(-1) for p in pending]).cpu().numpy()
+        self.flush_count += 1
         o = 0
         for t, l, dev in pending:
             rows = flat[o:o + dev.numel()].reshape(tuple(dev.shape))

@@ -16,6 +16,11 @@ masks the hot-path receivers consume.
     step so every intermediate is rounded to fp16 exactly where the reference's is.
   * t_test_neurons / ap_neurons / save_neuron_masks — modularity/paired_t_test.py:66-79,142 and
     modularity/skilled_neuron_ap.py:166-177: statistics -> the predictivity_{t}_{l}.json 0/1 masks RemoveNeurons reads.
+  * t_test_experts / expert_lists_from_statistics — modularity/paired_t_test_experts.py:47-65: the ExpertPredictivity
+    statistics (predictivity_{base,adj}_expert.json, diff_std_expert.json) -> expert id lists for save_expert_lists.
+  * accumulate_expert_counter / save_expert_counter — moefication/freq_expert_select.py:43-72 (and
+    modularity/moefy_skilled_experts.py:23-36): FrequencyMeasure label counters averaged over the images of a dataset
+    -> expert_counter_{topk}.json.
 """
 from __future__ import annotations
 
@@ -223,3 +228,66 @@ def save_neuron_masks(masks, path):
         for l, m in layers.items():
             with open(os.path.join(path, f"predictivity_{t}_{l}.json"), "w") as f:
                 json.dump([float(v) for v in np.asarray(m).reshape(-1) != 0], f)
+
+
+def t_test_experts(base_avg, adj_avg, diff_std, n_prompts, critical_value=3.579):
+    """Paired t-test of one (t, l) over experts (modularity/paired_t_test_experts.py:51-61): the sorted ids of the
+    experts with t < -critical_value, t as in t_test_neurons -- experts that score higher on the concept prompts."""
+    _, skilled = t_test_neurons(base_avg, adj_avg, diff_std, n_prompts, critical_value)
+    return [int(e) for e in np.flatnonzero(skilled)]
+
+
+def _json_or_path(obj):
+    if isinstance(obj, (str, os.PathLike)):
+        with open(obj) as f:
+            return json.load(f)
+    return obj
+
+
+def _cell(d, key):
+    """d[key] of a dict keyed by ints (in memory) or by their strings (read back from JSON)."""
+    return d[key] if key in d else d[str(key)]
+
+
+def expert_lists_from_statistics(base_json, adj_json, diff_std_json, n_prompts, critical_value=3.579):
+    """paired_t_test_experts.py:47-65 over every (t, l): base_json / adj_json are ExpertPredictivity's saved statistics
+    ({"time_steps": {t: {l: {"avg": [...], "std": [...]}}}}: StatMeter.save / to_json), diff_std_json the paired
+    {t: {l: [...]}} standard deviations of base - adj maxima; each a dict or the path of its JSON file. Returns
+    {t: {l: [expert ids]}} with int keys, ready for save_expert_lists."""
+    base, adj, diff = (_json_or_path(o) for o in (base_json, adj_json, diff_std_json))
+    out = {}
+    for tk, layers in base["time_steps"].items():
+        t = int(tk)
+        out[t] = {}
+        for lk in layers:
+            l = int(lk)
+            b = _cell(_cell(base["time_steps"], t), l)["avg"]
+            a = _cell(_cell(adj["time_steps"], t), l)["avg"]
+            out[t][l] = t_test_experts(b, a, _cell(_cell(diff, t), l), n_prompts, critical_value)
+    return out
+
+
+def accumulate_expert_counter(expert_counter, label_counter, layer_names, num_images):
+    """freq_expert_select.py:43-47,61-64 (moefy_skilled_experts.py:23-36): expert_counter[t][name][e] +=
+    label_counter[t][layer_names.index(name)][e] / num_images, in the reference's order (one division, one addition
+    per element and image). expert_counter None starts the {t: {name: [0] * E}} dict of the reference. Returns it."""
+    if expert_counter is None:
+        expert_counter = {t: {name: [0] * len(label_counter[t][layer_names.index(name)]) for name in layer_names}
+                          for t in label_counter}
+    for t in expert_counter:
+        for name in layer_names:
+            row = label_counter[t][layer_names.index(name)]
+            acc = expert_counter[t][name]
+            for e in range(len(acc)):
+                acc[e] += float(row[e]) / num_images
+    return expert_counter
+
+
+def save_expert_counter(expert_counter, path, topk):
+    """freq_expert_select.py:70-72: expert_counter_{topk}.json under `path` (the reference's JSON shape: timestep ->
+    layer name -> list of floats). Returns the file's path."""
+    os.makedirs(path, exist_ok=True)
+    fname = os.path.join(path, f"expert_counter_{topk}.json")
+    with open(fname, "w") as f:
+        json.dump(expert_counter, f)
+    return fname

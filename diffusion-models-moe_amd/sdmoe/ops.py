@@ -922,6 +922,46 @@ def expert_mean_topk(score, k: int, rows_per_img: int = 0, row_idx=None, mean_ou
     return topk_out
 
 
+def expert_stats(score, *, sel=None, rows_per_img=0, img_group=None, ngroups=1, colmax=None, count=None,
+                 workspace=None):
+    """Expert-level statistics of one routed call (sdmoe_expert_stats) over score [M, E] fp16 (a row-strided view is
+    fine) and sel (optional int32 [M, ceil(E / 32)], the sel_out of the routing kernels): colmax (optional fp16
+    [ngroups, E]) receives the maximum of each score column over the rows of the images of each group (image i =
+    rows_per_img rows, group img_group[i], int32 device [M / rows_per_img]; None = all group 0; rows_per_img 0 = one
+    image), count (optional int32 [M / rows_per_img, E]) the number of rows of each image whose sel bit is set.
+    workspace: fp32 scratch for the per-slab partials (default: the device's shared workspace). Returns
+    (colmax, count)."""
+    lib = _lib.load()
+    sp, lds = _rows(score, "score")
+    M, E = score.shape
+    rpi = int(rows_per_img)
+    if rpi < 0:
+        raise ValueError(f"expert_stats: rows_per_img = {rpi}")
+    nimg = M // rpi if rpi > 0 and M % rpi == 0 else min(M, 1)
+    selp = cp = cntp = igp = None
+    if sel is not None:
+        if tuple(sel.shape) != (M, (E + 31) // 32):
+            raise ValueError(f"expert_stats: sel {tuple(sel.shape)} is not {(M, (E + 31) // 32)}")
+        selp = _dev(sel, "sel", torch.int32)
+    if colmax is not None:
+        if tuple(colmax.shape) != (int(ngroups), E):
+            raise ValueError(f"expert_stats: colmax {tuple(colmax.shape)} is not {(int(ngroups), E)}")
+        cp = _dev(colmax, "colmax")
+        if img_group is not None:
+            if (rpi <= 0 or M % rpi == 0) and img_group.numel() != nimg:
+                raise ValueError(f"expert_stats: img_group has {img_group.numel()} entries for {nimg} images")
+            igp = _dev(img_group, "img_group", torch.int32)
+    if count is not None:
+        if (rpi <= 0 or M % rpi == 0) and tuple(count.shape) != (nimg, E):
+            raise ValueError(f"expert_stats: count {tuple(count.shape)} is not {(nimg, E)}")
+        cntp = _dev(count, "count", torch.int32)
+    ws = _workspace(score.device) if workspace is None else workspace
+    st = lib.sdmoe_expert_stats(sp, lds, selp, M, E, rpi, igp, int(ngroups), cp, cntp,
+                                _dev(ws, "workspace", torch.float32), ws.numel(), _stream())
+    _lib.check(st, "sdmoe_expert_stats")
+    return colmax, count
+
+
 def colnorm_accum(P, sumsq):
     """Wanda column statistic (wanda_receiver.py:37-57): sumsq[f] += sum_m (P[m,f] / ||P[m,:]||_2)^2."""
     lib = _lib.load()

@@ -327,6 +327,25 @@ int sdmoe_wmask_kmajor(const void* bits, long ldb, int N, int K, const int* perm
 int sdmoe_expert_mean_topk(const void* score, long ld_score, int M, int E, int rows_per_img, const int* row_idx,
                            int n_idx, int k, void* mean_out, int* topk_out, float* workspace, long workspace_floats,
                            void* stream);
+/*
+ * sdmoe_expert_stats — the expert-level statistics of ExpertPredictivity.hook_fn (neuron_receivers/
+ * expert_activation.py:51-59) and FrequencyMeasure.hook_fn (neuron_receivers/frequency_measure.py:53-57) as one
+ * streaming pass over what the routing kernels already produce: score [M, E] fp16 (row stride ld_score) and sel
+ * [M, ceil(E / 32)] uint32 words, bit e % 32 of word e / 32 = expert e among the token's top-k (the sel_out of
+ * sdmoe_geglu_route, sdmoe_moe_topk_mask and sdmoe_moe_topk_keep; nullable).
+ *   colmax (nullable, fp16 [ngroups, E]): colmax[g][e] = max of score[m][e] over every row of every image i with
+ *     img_group[i] == g (image i = rows [i * rows_per_img, (i + 1) * rows_per_img); img_group NULL = one group;
+ *     rows_per_img 0 = one image of M rows) -- torch.max(score, dim=0). The maximum starts from -inf (a GELU expert's
+ *     score can be negative on every row); a group without an image gets -inf.
+ *   count (nullable, int32 [M / rows_per_img, E]): count[i][e] = rows of image i whose sel bit e is set; bits at or
+ *     above E in the last word are ignored. count without sel is SDMOE_EARG.
+ * No atomics: deterministic. E <= 256 (SDMOE_ESHAPE); M == 0 is a no-op; M % rows_per_img == 0 (SDMOE_EARG).
+ * workspace >= c * [count != NULL] + ceil(c / 2) * [colmax != NULL] floats, c = (M / rows_per_img) *
+ * ceil(rows_per_img / 16) * E (SDMOE_ESHAPE).
+ */
+int sdmoe_expert_stats(const void* score, long ld_score, const unsigned* sel, int M, int E, int rows_per_img,
+                       const int* img_group, int ngroups, void* colmax, int* count, float* workspace,
+                       long workspace_floats, void* stream);
 int sdmoe_colnorm_accum(const void* P, long ldp, int M, int F, float* sumsq, float* workspace, long workspace_floats,
                         void* stream);
 int sdmoe_wanda_mask(const void* W, long ldw, int C, int F, const void* norm_base, const void* norm_adj, int kprune,
