@@ -5,7 +5,8 @@ RemoveExperts, RemoveNeurons, WandaRemoveNeuronsFast, WandaRemovePerPrompt, Mult
 receivers that produce their inputs (GetExperts -> expert lists, Wanda -> column norms -> masks, NeuronPredictivity /
 NeuronPredictivityBB -> max-activation statistics -> paired t-test or AP neuron masks; ExpertPredictivity -> per-expert
 maximum routing scores -> paired t-test -> expert lists) and FrequencyMeasure, the per-expert
-selection histogram for choosing topk_experts. The remaining receivers of the reference (AddExperts, SparsityMeasure,
+selection histogram for choosing topk_experts, and SparsityMeasure, the gate-sparsity counts of a relufied U-Net (the
+measurement behind sparsity/check_sparsity.py's sparsity.json). The remaining receivers of the reference (AddExperts,
 SaveStates and the HPO receivers) are not exported.
 """
 from neuron_receivers.base_receiver import BaseNeuronReceiver, GEGLU, GELU  # noqa: F401
@@ -20,4 +21,5 @@ from neuron_receivers.multi_concept_remover import MultiConceptRemoverWanda  # n
 from neuron_receivers.get_experts import GetExperts  # noqa: F401
 from neuron_receivers.expert_activation import ExpertPredictivity  # noqa: F401
 from neuron_receivers.frequency_measure import FrequencyMeasure  # noqa: F401
+from neuron_receivers.sparsity_measure import SparsityMeasure  # noqa: F401
 from neuron_receivers.wanda_receiver import Wanda  # noqa: F401

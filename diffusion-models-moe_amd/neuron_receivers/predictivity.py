@@ -21,12 +21,11 @@ from __future__ import annotations
 
 import torch
 
-from sdmoe._lib import SdmoeError
-
 from neuron_receivers.base_receiver import GEGLU, BaseNeuronReceiver
+from neuron_receivers.prompt_groups import PromptGroups
 
 
-class NeuronPredictivity(BaseNeuronReceiver):
+class NeuronPredictivity(PromptGroups, BaseNeuronReceiver):
     def __init__(self, seed, T, n_layers, replace_fn=GEGLU, keep_nsfw=False, hook_module='unet', **kw):
         super().__init__(seed, replace_fn, keep_nsfw, hook_module, **kw)
         self.T = T
@@ -72,28 +71,7 @@ class NeuronPredictivity(BaseNeuronReceiver):
         self._max_gate = None  # predictivity.py:35-39: the per-prompt maxima start over
         self._pending = []
 
-    # ---- prompt groups ---------------------------------------------------------------------------------------------
-    def set_prompts(self, ann):
-        """Fix the grouping of the next calls: a prompt string (or None) is one group over every image, a list of B
-        prompts gives B groups."""
-        self._nprompts = None if ann is None or isinstance(ann, str) else len(ann)
-        self._img_tables = {}
-
-    def image_table(self, nimg):
-        """Prompt of each of the call's nimg U-Net images: i % B for B or, under guidance, 2 B images."""
-        B = self._nprompts
-        if B and nimg in (B, 2 * B):
-            return [i % B for i in range(nimg)]
-        raise SdmoeError(f"the call runs {nimg} U-Net images, but {B} prompts were configured (expected {B} or, with "
-                         f"guidance, {2 * B if B else 0} images)")
-
-    def _image_table_dev(self, nimg, device):
-        key = (nimg, device)
-        tab = self._img_tables.get(key)
-        if tab is None:
-            tab = self._img_tables[key] = torch.tensor(self.image_table(nimg), dtype=torch.int32, device=device)
-        return tab
-
+    # ---- prompt groups: set_prompts / image_table / _image_table_dev come from PromptGroups (prompt_groups.py) ------
     def position_bits(self, module, seq_len, device):
         """Token positions that enter the maximum (None: all of them). NeuronPredictivityBB narrows them."""
         return None

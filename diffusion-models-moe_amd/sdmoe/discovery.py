@@ -21,6 +21,9 @@ masks the hot-path receivers consume.
   * accumulate_expert_counter / save_expert_counter — moefication/freq_expert_select.py:43-72 (and
     modularity/moefy_skilled_experts.py:23-36): FrequencyMeasure label counters averaged over the images of a dataset
     -> expert_counter_{topk}.json.
+  * sparsity_ratios / accumulate_sparsity / neuron_zero_fraction — sparsity/check_sparsity.py:34-46 from the device
+    counts of SparsityMeasure: the per-call zero ratio, the StatMeter behind sparsity.json, and per-neuron zero
+    fractions.
 """
 from __future__ import annotations
 
@@ -291,3 +294,40 @@ def save_expert_counter(expert_counter, path, topk):
     with open(fname, "w") as f:
         json.dump(expert_counter, f)
     return fname
+
+
+def sparsity_ratios(calls):
+    """SparsityMeasure.calls -> float64 [calls, groups]: zeros / elements per hooked call and group of images, the
+    exact value of check_sparsity.py:41-45's "mean over tokens of (zeros in the row / F)" (every row has F elements, so
+    the mean of the row ratios is the ratio of the sums; the reference evaluates it in fp32 and differs by rounding)."""
+    if not len(calls):
+        return np.zeros((0, 0), dtype=np.float64)
+    zeros = np.stack([np.asarray(c["zeros"], dtype=np.int64) for c in calls])
+    elements = np.stack([np.asarray(c["elements"], dtype=np.int64) for c in calls])
+    return zeros.astype(np.float64) / elements.astype(np.float64)
+
+
+def accumulate_sparsity(meter, ratios, num_geglu):
+    """check_sparsity.py:34-46: hooked call i of a pipeline call updates StatMeter cell (i // num_geglu, i % num_geglu)
+    with its zero ratio, once per prompt (column of `ratios`, [calls] or [calls, prompts]), prompt by prompt as the
+    reference's dataset loop does. StatMeter.save then writes sparsity.json. Returns the meter."""
+    r = np.asarray(ratios, dtype=np.float64)
+    r = r[:, None] if r.ndim == 1 else r
+    for p in range(r.shape[1]):
+        for i in range(r.shape[0]):
+            meter.update(float(r[i, p]), i // num_geglu, i % num_geglu)
+    return meter
+
+
+def neuron_zero_fraction(calls, num_geglu):
+    """Per (timestep, layer) and neuron, the fraction of a group's rows whose gate counted as zero, from the
+    per_neuron=True records of SparsityMeasure.calls: {t: {l: float64 [groups, F]}} (this port's addition: a neuron at
+    1.0 is dead on that prompt, and neurons that are zero together are candidates for one expert)."""
+    out = {}
+    for i, c in enumerate(calls):
+        if "neuron_zeros" not in c:
+            raise ValueError("neuron_zero_fraction needs the records of SparsityMeasure(per_neuron=True)")
+        nz = np.asarray(c["neuron_zeros"], dtype=np.float64)
+        rows = np.asarray(c["rows"], dtype=np.float64).reshape(-1, 1)
+        out.setdefault(i // num_geglu, {})[i % num_geglu] = nz / rows
+    return out

@@ -904,6 +904,54 @@ def geglu_neurons(y, act=ACT_GELU, *, override_bits=None, override_value=0.0, ga
     return out
 
 
+def geglu_sparsity(y, act=ACT_GELU, *, threshold=0.0, rows_per_img=0, img_group=None, ngroups=1, col_zero=None,
+                   col_neg=None, totals=None, out=None, workspace=None, gate_out=None):
+    """Dense GEGLU over y = proj(x) [M, 2F] with the gate-sparsity counts of the same pass (sdmoe_geglu_sparsity):
+    out = value * g, g = act(gate), bit-identical to geglu_neurons without an override; per group of images (image i =
+    rows_per_img rows, group img_group[i], int32 device [M / rows_per_img]; None = all group 0) and neuron, col_zero
+    (optional int32 [ngroups, F]) receives the number of rows with |g| <= threshold (fp32 compare; 0.0 counts the exact
+    zeros of either sign), col_neg (optional int32 [ngroups, F]) the rows with g < 0, totals (optional int64
+    [ngroups, 2]) their sums over the neurons. Either totals or both arrays must be given; every given buffer is
+    written in full (none needs zeroing). gate_out (optional [M, F]) receives g. workspace: fp32 scratch for the
+    per-slab partial counts (default: the device's shared workspace). Returns out."""
+    lib = _lib.load()
+    if act == ACT_GELU:
+        ensure_gelu_table(y.device)
+    yp, ldy = _rows(y, "y")
+    M = y.shape[0]
+    F = y.shape[1] // 2
+    if out is None:
+        out = torch.empty((M, F), dtype=torch.float16, device=y.device)
+    op, ldo = _rows(out, "out")
+    if tuple(out.shape) != (M, F):
+        raise ValueError(f"geglu_sparsity: out {tuple(out.shape)} is not {(M, F)}")
+    gp, ldg = (None, 0) if gate_out is None else _rows(gate_out, "gate_out")
+    if gate_out is not None and tuple(gate_out.shape) != (M, F):
+        raise ValueError(f"geglu_sparsity: gate_out {tuple(gate_out.shape)} is not {(M, F)}")
+    if totals is None and (col_zero is None or col_neg is None):
+        raise ValueError("geglu_sparsity: give totals, or both col_zero and col_neg")
+    rpi = int(rows_per_img)
+    nimg = M // rpi if rpi > 0 and M % rpi == 0 else 1
+    ptrs = {}
+    for name, t, shape, dtype in (("col_zero", col_zero, (int(ngroups), F), torch.int32),
+                                  ("col_neg", col_neg, (int(ngroups), F), torch.int32),
+                                  ("totals", totals, (int(ngroups), 2), torch.int64)):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"geglu_sparsity: {name} {tuple(t.shape)} is not {shape}")
+        ptrs[name] = None if t is None else _dev(t, name, dtype)
+    igp = None
+    if img_group is not None:
+        if (rpi <= 0 or M % rpi == 0) and img_group.numel() != nimg:
+            raise ValueError(f"geglu_sparsity: img_group has {img_group.numel()} entries for {nimg} images")
+        igp = _dev(img_group, "img_group", torch.int32)
+    ws = _workspace(y.device) if workspace is None else workspace
+    st = lib.sdmoe_geglu_sparsity(yp, ldy, M, F, act, float(threshold), op, ldo, gp, ldg, rpi, igp, int(ngroups),
+                                  ptrs["col_zero"], ptrs["col_neg"], ptrs["totals"],
+                                  _dev(ws, "workspace", torch.float32), ws.numel(), _stream())
+    _lib.check(st, "sdmoe_geglu_sparsity")
+    return out
+
+
 def expert_mean_topk(score, k: int, rows_per_img: int = 0, row_idx=None, mean_out=None, topk_out=None):
     """GetExperts statistic (get_experts.py:72-80): mean of the fp16 expert scores [M, E] over all tokens, or
     over positions row_idx (int32 device tensor) of every rows_per_img-row image, then the top-k expert ids

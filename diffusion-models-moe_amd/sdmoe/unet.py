@@ -300,6 +300,30 @@ class GEGLU(nn.Module):
         out = out.view(*shp[:-1], self.inner_dim)
         return out, (gate.view(*shp[:-1], self.inner_dim) if want_gate else None)
 
+    def sparsity(self, x, threshold=0.0, col_zero=None, col_neg=None, totals=None, img_group=None, ngroups=1,
+                 want_gate=False):
+        """proj GEMM + the gate-sparsity streaming pass (ops.geglu_sparsity), ignoring any MoE routing: value *
+        act(gate) in the natural neuron order -- the product of neurons() without an override, bit for bit -- and, per
+        group of the images x[i], the per-neuron counts of rows with |act(gate)| <= threshold (col_zero, int32
+        [ngroups, 4C]) and with act(gate) < 0 (col_neg), and their sums over the neurons (totals, int64 [ngroups, 2])
+        (SparsityMeasure, neuron_receivers/sparsity_measure.py:13-18 with the counting of sparsity/
+        check_sparsity.py:41-46 done on the device). x: [images, tokens, C] (or [tokens, C]: one image). Returns
+        (out, act(gate) or None)."""
+        shp = x.shape
+        x2 = x.reshape(-1, shp[-1])
+        norm = self._take_ln(x)
+        if norm is not None:
+            x2 = ops.layernorm(x2, norm.weight, norm.bias, norm.eps)
+        self._out_perm = None
+        self._out_keep = None
+        y = self.proj.run(x2)
+        gate = torch.empty((x2.shape[0], self.inner_dim), dtype=torch.float16, device=x.device) if want_gate else None
+        out = ops.geglu_sparsity(y, act_code(self.gelu), threshold=threshold,
+                                 rows_per_img=shp[-2] if x.dim() >= 3 else 0, img_group=img_group, ngroups=ngroups,
+                                 col_zero=col_zero, col_neg=col_neg, totals=totals, gate_out=gate)
+        out = out.view(*shp[:-1], self.inner_dim)
+        return out, (gate.view(*shp[:-1], self.inner_dim) if want_gate else None)
+
     def forward(self, x, scale=1.0):
         if self._sdmoe_deferred and self._forward_hooks:
             return None  # a sdmoe receiver hook computes the routed output (no double compute)

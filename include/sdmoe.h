@@ -374,6 +374,28 @@ int sdmoe_geglu_neurons(const void* Y, long ldy, int M, int F, int act, const un
                         long workspace_floats, void* stream);
 
 /*
+ * sdmoe_geglu_sparsity — the gate-sparsity measurement: SparsityMeasure.hook_fn / .test (neuron_receivers/
+ * sparsity_measure.py:13-18, :39-41) and the per-call count of sparsity/check_sparsity.py:41-46 as one streaming pass
+ * over Y = proj(x) = [value | gate] [M, 2F] (row stride ldy), in place of a host copy of every activated gate:
+ *   g   = fp16(act(gate))                  the activation of sdmoe_geglu_neurons (the registered GELU table, else erf)
+ *   out = fp16(float(value) * float(g))    [M, F] (ldo), bit-identical to sdmoe_geglu_neurons without an override;
+ *                                          gate_out (nullable, ldg) = g
+ *   col_zero (nullable, int32 [ngroups, F]): col_zero[img_group[i]][n] = rows of image i = rows [i * rows_per_img,
+ *     (i + 1) * rows_per_img) with |float(g)| <= threshold (fp32 compare; threshold 0 counts +0 and -0: `gate == 0.0`);
+ *     img_group NULL = every image in group 0; rows_per_img 0 = one image of M rows; a group without an image gets 0
+ *   col_neg (nullable, int32 [ngroups, F]): the rows with float(g) < 0 (-0 is not counted: `gate >= 0` holds for it)
+ *   totals (nullable, int64 [ngroups, 2]): {sum_n col_zero[g][n], sum_n col_neg[g][n]}
+ * col_zero and col_neg may be NULL when totals is given; totals may be NULL when both arrays are given (else
+ * SDMOE_EARG). Every output is written in full by each call (no buffer is assumed zeroed); integer sums only, so the
+ * results do not depend on the order of the blocks. threshold >= 0 (SDMOE_EARG); M == 0 is a no-op.
+ * F % 32 == 0, ldy % 8 == 0 (SDMOE_ESHAPE); M % rows_per_img == 0 (SDMOE_EARG).
+ * workspace >= (M / rows_per_img) * ceil(rows_per_img / 64) * F floats (SDMOE_ESHAPE).
+ */
+int sdmoe_geglu_sparsity(const void* Y, long ldy, int M, int F, int act, float threshold, void* out, long ldo,
+                         void* gate_out, long ldg, int rows_per_img, const int* img_group, int ngroups, int* col_zero,
+                         int* col_neg, int64_t* totals, float* workspace, long workspace_floats, void* stream);
+
+/*
  * Offline MoE-fication: ParamSplit.split (moefication/moe_utils.py:97-107) clusters the
  * L2-normalised gate rows of each GEGLU with KMeansConstrained(size_min = size_max = expert_size).
  * sdmoe_sqdist_f32 — D[i][c] = max(|x_i|^2 + |c_c|^2 - 2 x_i.c_c, 0), fp32 device arrays (exact fp32 MFMA
