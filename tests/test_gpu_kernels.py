@@ -326,6 +326,9 @@ def test_cfg_ddim_step_and_prepare():
     ref = math.sqrt(a_p) * x0 + math.sqrt(1 - a_p) * ee
     ops.cfg_ddim_step(eps, lat, True, g, a_t, a_p, next_in=x_in)
     close(lat, ref, tol=1e-4)
+    next_ref = lat.permute(0, 2, 3, 1).reshape(B * H * H, 4).half()
+    assert torch.equal(x_in[:B * H * H, :4], next_ref) and torch.equal(x_in[B * H * H:, :4], next_ref)
+    assert x_in[:, 4:].abs().max().item() == 0
 
 
 # ---- the bench workload's exact shapes (SD-1.4 512^2, U-Net batch 16: 64x64 latents = 65,536 rows) ----------
