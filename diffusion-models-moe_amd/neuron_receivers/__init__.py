@@ -6,8 +6,10 @@ receivers that produce their inputs (GetExperts -> expert lists, Wanda -> column
 NeuronPredictivityBB -> max-activation statistics -> paired t-test or AP neuron masks; ExpertPredictivity -> per-expert
 maximum routing scores -> paired t-test -> expert lists) and FrequencyMeasure, the per-expert
 selection histogram for choosing topk_experts, and SparsityMeasure, the gate-sparsity counts of a relufied U-Net (the
-measurement behind sparsity/check_sparsity.py's sparsity.json). The remaining receivers of the reference (AddExperts,
-SaveStates and the HPO receivers) are not exported.
+measurement behind sparsity/check_sparsity.py's sparsity.json); the HPO path (BaseUNetReceiver, RemoveNeuronsHPO,
+RemoveNeuronsNoiseHPO: the receivers modularity/remove_experts_hpo.py and remove_experts_noise_hpo.py drive, the noise
+objective computed on the device by sdmoe_noise_distance) and SaveStates. The one remaining receiver of the reference,
+AddExperts, is not exported.
 """
 from neuron_receivers.base_receiver import BaseNeuronReceiver, GEGLU, GELU  # noqa: F401
 from neuron_receivers.predictivity import NeuronPredictivity  # noqa: F401
@@ -23,3 +25,7 @@ from neuron_receivers.expert_activation import ExpertPredictivity  # noqa: F401
 from neuron_receivers.frequency_measure import FrequencyMeasure  # noqa: F401
 from neuron_receivers.sparsity_measure import SparsityMeasure  # noqa: F401
 from neuron_receivers.wanda_receiver import Wanda  # noqa: F401
+from neuron_receivers.base_unet_receiver import BaseUNetReceiver  # noqa: F401
+from neuron_receivers.remove_skilled_neurons_hpo import RemoveNeuronsHPO  # noqa: F401
+from neuron_receivers.remove_skilled_neurons_noise_hpo import RemoveNeuronsNoiseHPO  # noqa: F401
+from neuron_receivers.save_states import SaveStates  # noqa: F401

@@ -24,6 +24,9 @@ masks the hot-path receivers consume.
   * sparsity_ratios / accumulate_sparsity / neuron_zero_fraction — sparsity/check_sparsity.py:34-46 from the device
     counts of SparsityMeasure: the per-call zero ratio, the StatMeter behind sparsity.json, and per-neuron zero
     fractions.
+  * noise_distances / NoiseObjective — modularity/remove_experts_noise_hpo.py:39-45, 73-87, 124-131: the float64 sums
+    of sdmoe_noise_distance -> the driver's two distances per step and prompt, its per-step averages, the trial's score
+    and noise_diff_per_sample.json.
 """
 from __future__ import annotations
 
@@ -331,3 +334,53 @@ def neuron_zero_fraction(calls, num_geglu):
         rows = np.asarray(c["rows"], dtype=np.float64).reshape(-1, 1)
         out.setdefault(i // num_geglu, {})[i % num_geglu] = nz / rows
     return out
+
+
+def noise_distances(stats):
+    """ops.noise_distance's [T, G, 4] sums (a device or host tensor, or an array) -> (l2 [T, G], l1n [T, G]) float64
+    arrays: l2 = sqrt(S (a - b)^2), the driver's torch.norm(a - b) (remove_experts_noise_hpo.py:75), and l1n =
+    sqrt(S (a / max(|a|_1, 1e-12) - b / max(|b|_1, 1e-12))^2), its distance of the F.normalize(p = 1)'d vectors (:78-84).
+    One device->host copy of 4 T G doubles when stats is on a device."""
+    s = stats.detach().cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats)
+    s = s.astype(np.float64, copy=False)
+    if s.ndim != 3 or s.shape[2] != 4:
+        raise ValueError(f"noise_distances: expected [T, G, 4] sums, got {s.shape}")
+    return np.sqrt(s[:, :, 0]), np.sqrt(s[:, :, 3])
+
+
+class NoiseObjective:
+    """The bookkeeping of the noise-HPO driver's remove_experts (modularity/remove_experts_noise_hpo.py:39-45, 73-87,
+    124-131) over the samples (prompt pairs) of one trial: noise_diff[t] is an Average of l2 over the samples,
+    avg_noise_diff the mean over the steps of those averages (the trial's score, minimised), noise_diff_per_sample[i]
+    the mean over the steps of sample i's l1n."""
+
+    def __init__(self, T):
+        self.T = int(T)
+        self.noise_diff = {t: Average() for t in range(self.T)}
+        self.noise_diff_per_sample = {}
+
+    def update(self, l2, l1n):
+        """One sample ([T] arrays) or, from a prompt batch, G samples in prompt order ([T, G] arrays, the two outputs of
+        noise_distances)."""
+        l2 = np.asarray(l2, dtype=np.float64).reshape(self.T, -1)
+        l1n = np.asarray(l1n, dtype=np.float64).reshape(self.T, -1)
+        if l2.shape != l1n.shape:
+            raise ValueError(f"NoiseObjective.update: l2 {l2.shape} and l1n {l1n.shape} differ")
+        for g in range(l2.shape[1]):
+            i = len(self.noise_diff_per_sample)
+            per_sample = 0.0
+            for t in range(self.T):
+                self.noise_diff[t].update(float(l2[t, g]))
+                per_sample += float(l1n[t, g])
+            self.noise_diff_per_sample[i] = per_sample / self.T
+
+    @property
+    def avg_noise_diff(self):
+        return sum(self.noise_diff[t].avg for t in range(self.T)) / self.T
+
+    def save(self, path):
+        """noise_diff_per_sample.json (:189-190) in `path` (a directory) or at `path` (a .json file name)."""
+        fname = path if path.endswith(".json") else os.path.join(path, "noise_diff_per_sample.json")
+        with open(fname, "w") as f:
+            json.dump(self.noise_diff_per_sample, f)
+        return fname

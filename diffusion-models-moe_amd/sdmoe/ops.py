@@ -952,6 +952,67 @@ def geglu_sparsity(y, act=ACT_GELU, *, threshold=0.0, rows_per_img=0, img_group=
     return out
 
 
+NOISE_SLAB_ROWS = 1024  # rows per partial sum of sdmoe_noise_distance (its workspace bound, include/sdmoe.h)
+
+
+def noise_capture(eps, store):
+    """Channels 0..3 of every row of eps (fp16 [rows, >= 4], e.g. the pipeline's padded U-Net output) -> store (fp16
+    [rows, >= 4]; a compact [rows, 4] step slice of a [T, rows, 4] noise store), on the current stream
+    (sdmoe_noise_capture). Columns past 3 of either are never touched. Returns store."""
+    lib = _lib.load()
+    ep, lde = _rows(eps, "eps")
+    sp, lds = _rows(store, "store")
+    if eps.shape[0] != store.shape[0] or eps.shape[1] < 4 or store.shape[1] < 4:
+        raise ValueError(f"noise_capture: eps {tuple(eps.shape)} and store {tuple(store.shape)} need the same rows and "
+                         f">= 4 channels")
+    _lib.check(lib.sdmoe_noise_capture(ep, lde, sp, lds, eps.shape[0], _stream()), "sdmoe_noise_capture")
+    return store
+
+
+def noise_distance(a, b, nimg, *, img_group=None, ngroups=1, out=None, workspace=None):
+    """The noise-HPO sums of two stores of per-step U-Net outputs (sdmoe_noise_distance): a, b fp16 [T, nimg * HW, ld]
+    (ld >= 4, the row and step strides multiples of 4; only channels 0..3 are read); image i of a step belongs to group
+    img_group[i] (int32 device [nimg]; None: one group). Returns the device float64 [T, ngroups, 4] of
+    {S (a - b)^2, A = S |a|, B = S |b|, S (a / max(A, 1e-12) - b / max(B, 1e-12))^2} per step and group, accumulated in
+    float64 in a fixed order (bit-identical from run to run). workspace: float64 scratch of at least
+    4 * T * nimg * ceil(HW / 1024) values (default: allocated per call -- a few KB)."""
+    lib = _lib.load()
+    for name, t in (("a", a), ("b", b)):
+        if t.dim() != 3:
+            raise ValueError(f"noise_distance: {name} must be [T, nimg * HW, ld], got {tuple(t.shape)}")
+        if not t.is_cuda:
+            raise _lib.SdmoeError(f"noise_distance: {name} is not on a GPU device; sdmoe has no CPU path")
+        if t.dtype != torch.float16:
+            raise TypeError(f"noise_distance: {name}: expected float16, got {t.dtype}")
+        if t.stride(2) != 1 and t.shape[2] > 1:
+            raise ValueError(f"noise_distance: {name}: inner dimension must be contiguous")
+    if a.shape[:2] != b.shape[:2] or a.device != b.device:
+        raise ValueError(f"noise_distance: a {tuple(a.shape)} and b {tuple(b.shape)} differ in steps, rows or device")
+    T, rows = a.shape[0], a.shape[1]
+    nimg = int(nimg)
+    if nimg <= 0 or rows % nimg:
+        raise ValueError(f"noise_distance: {rows} rows per step are not {nimg} images")
+    HW = rows // nimg
+    if a.shape[2] < 4 or b.shape[2] < 4:
+        raise ValueError("noise_distance: a and b need >= 4 channels")
+    igp = None
+    if img_group is not None:
+        if img_group.numel() != nimg:
+            raise ValueError(f"noise_distance: img_group has {img_group.numel()} entries for {nimg} images")
+        igp = _dev(img_group, "img_group", torch.int32)
+    if out is None:
+        out = torch.empty((T, int(ngroups), 4), dtype=torch.float64, device=a.device)
+    elif tuple(out.shape) != (T, int(ngroups), 4):
+        raise ValueError(f"noise_distance: out {tuple(out.shape)} is not {(T, int(ngroups), 4)}")
+    if workspace is None:
+        workspace = torch.empty(4 * T * nimg * -(-HW // NOISE_SLAB_ROWS), dtype=torch.float64, device=a.device)
+    st = lib.sdmoe_noise_distance(a.data_ptr(), a.stride(1), a.stride(0), b.data_ptr(), b.stride(1), b.stride(0), T,
+                                  nimg, HW, igp, int(ngroups), _dev(out, "out", torch.float64),
+                                  _dev(workspace, "workspace", torch.float64), workspace.numel(), _stream())
+    _lib.check(st, "sdmoe_noise_distance")
+    return out
+
+
 def expert_mean_topk(score, k: int, rows_per_img: int = 0, row_idx=None, mean_out=None, topk_out=None):
     """GetExperts statistic (get_experts.py:72-80): mean of the fp16 expert scores [M, E] over all tokens, or
     over positions row_idx (int32 device tensor) of every rows_per_img-row image, then the top-k expert ids

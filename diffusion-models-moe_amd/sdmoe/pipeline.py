@@ -120,6 +120,18 @@ class PipelineOutput:
     images: list
 
 
+class _HookHandle:
+    """Returned by StableDiffusionPipeline.register_unet_output_hook: remove() takes the hook off again (once)."""
+
+    def __init__(self, hooks, fn):
+        self._hooks, self._fn = hooks, fn
+
+    def remove(self):
+        if self._fn is not None and self._fn in self._hooks:
+            self._hooks.remove(self._fn)
+        self._fn = None
+
+
 class StableDiffusionPipeline:
     def __init__(self, unet: UNet2DConditionModel, device="cuda", num_inference_steps=50, guidance_scale=7.5,
                  scheduler="ddim", vae=None, text_encoder=None, tokenizer=None, text_encoder_2=None,
@@ -140,6 +152,22 @@ class StableDiffusionPipeline:
         self.tokenizer = tokenizer
         self.text_encoder_2 = text_encoder_2
         self.tokenizer_2 = tokenizer_2
+        self._unet_output_hooks = []  # register_unet_output_hook
+
+    def register_unet_output_hook(self, fn):
+        """Call fn(step_index, eps, nimg, HW) after every U-Net evaluation of the denoising loop, before the scheduler
+        step consumes it -- the seam of `model.unet.register_forward_hook` in the reference's BaseUNetReceiver /
+        RemoveNeuronsNoiseHPO (the loop calls unet.forward_nhwc, so a module forward hook never fires). eps is the
+        loop's live fp16 [nimg * HW, OUT_PAD] buffer: channels 0..3 are the prediction, rows are [uncond x B ; cond x
+        B] images of HW positions, and the next step overwrites it -- valid during the call only (copy what you keep:
+        ops.noise_capture). step_index counts U-Net calls (0..49 for DDIM, 0..50 for PNDM at 50 steps). The return
+        value is ignored. Returns a handle whose .remove() unregisters fn."""
+        self._unet_output_hooks.append(fn)
+        return _HookHandle(self._unet_output_hooks, fn)
+
+    def _after_unet(self, step_index, eps, HW):
+        for fn in tuple(self._unet_output_hooks):
+            fn(step_index, eps, eps.shape[0] // HW, HW)
 
     @classmethod
     def synthetic(cls, cfg: UNetConfig | None = None, seed: int = 0, device="cuda", **kw):
@@ -230,6 +258,8 @@ class StableDiffusionPipeline:
     def _denoise(self, bufs, steps, g, do_cfg):
         """The denoising loop over bufs (lat, x_in, eps, ctx, add_hidden)."""
         lat, x_in, eps, ctx, add_hidden = (bufs[k] for k in ("lat", "x_in", "eps", "ctx", "add_hidden"))
+        hooks = self._unet_output_hooks  # register_unet_output_hook: empty = the bare loop
+        HW = self.config.sample_size * self.config.sample_size
 
         def temb_row(table, i):
             return None if table is None else table[i:i + 1]
@@ -245,6 +275,8 @@ class StableDiffusionPipeline:
             for i, (t, coef, flags) in enumerate(plan):
                 def body(i=i, t=t, coef=coef, flags=flags):
                     self.unet.forward_nhwc(x_in, float(t), ctx, out=eps, add_hidden=add_hidden, temb=temb_row(table, i))
+                    if hooks:
+                        self._after_unet(i, eps, HW)
                     ops.cfg_multistep_step(eps, lat, do_cfg, g, hist, cur, coef, flags, next_in=x_in)
                 body()
         else:
@@ -255,6 +287,8 @@ class StableDiffusionPipeline:
             for s, t in enumerate(ts):
                 def body(s=s, t=t):
                     self.unet.forward_nhwc(x_in, float(t), ctx, out=eps, add_hidden=add_hidden, temb=temb_row(table, s))
+                    if hooks:
+                        self._after_unet(s, eps, HW)
                     ops.cfg_ddim_step(eps, lat, do_cfg, g, a_t[s], a_prev[s], next_in=x_in)
                 body()
 

@@ -477,6 +477,27 @@ int sdmoe_cfg_multistep_step(const void* eps, long lde, float* lat, int B, int H
                              void* stream);
 
 /*
+ * The noise-HPO objective (the reference's modularity/remove_experts_noise_hpo.py:74-84) on device stores of the
+ * U-Net's per-step output.
+ * sdmoe_noise_capture: channels 0..3 of each of `rows` fp16 rows of eps (leading dimension lde, e.g. the pipeline's
+ *   padded eps buffer) -> fp16 row r of store (leading dimension lds; 4 for a compact [rows, 4] step slice of a
+ *   [T, nimg * HW, 4] store). lde, lds >= 4 and multiples of 4, both pointers 8-byte aligned. Runs on `stream`.
+ * sdmoe_noise_distance: a, b fp16; step t's rows [nimg * HW] start at a + t * step_a (elements), row stride lda
+ *   (>= 4, a multiple of 4, as the steps; pointers 8-byte aligned); only channels 0..3 of a row are read. Image i
+ *   (rows [i * HW, (i + 1) * HW)) belongs to group img_group[i] (int32 device [nimg]; NULL: one group, ngroups must
+ *   be 1; images whose entry is outside [0, ngroups) belong to no group). out: float64 [T, ngroups, 4] =
+ *     { S (a - b)^2,  A = S |a|,  B = S |b|,  S (a / max(A, 1e-12) - b / max(B, 1e-12))^2 }
+ *   over the elements of the group's images (the host takes the square roots: torch.norm(a - b), and the distance of
+ *   the F.normalize(p = 1)'d vectors); a group without images gives zeros. All arithmetic is float64, the fourth
+ *   sum is taken element by element with IEEE divisions (no expanded form). Fixed-order partial sums, no atomics:
+ *   results are bit-identical from run to run. workspace: 4 * T * nimg * ceil(HW / 1024) doubles, 8-byte aligned.
+ */
+int sdmoe_noise_capture(const void* eps, long lde, void* store, long lds, long rows, void* stream);
+int sdmoe_noise_distance(const void* a, long lda, long step_a, const void* b, long ldb, long step_b, int T, int nimg,
+                         int HW, const int* img_group, int ngroups, double* out, double* workspace,
+                         long workspace_doubles, void* stream);
+
+/*
  * Tuning knobs for A/B experiments: process-wide integers the launch code reads. Ids, legal values and defaults are
  * ABI (recorded command lines name them). This is the one definition of what each value means; the library's table
  * (csrc/tune.hip) holds id, name, default and legal set. sdmoe_tune returns -1 for an unknown knob or an illegal
