@@ -6,11 +6,12 @@
 //     FrequencyMeasure.hook_fn (neuron_receivers/frequency_measure.py:53-57): how many tokens of each image selected
 //       each expert (the reference's Python loop over labels[0])
 // HBM-streaming, no MFMA, E <= 256 of any value: a block is 64 expert columns x 4 row lanes, so a wave reads 128
-// contiguous bytes of one score row and broadcasts two sel words; fixed row slabs that never straddle an image. Each
+// contiguous bytes of one score row and broadcasts two sel words; the slab plan and the group walk are geglu_stream.h's
+// (the row loop is this file's own: it reads scores and sel words, not the seam). Each
 // block keeps a running fp16 maximum (from -inf: a GELU expert's score can be negative on every row) and an int32
 // count per column and writes one partial row of each; a second small kernel combines the slabs of each group /
 // image. No atomics: a maximum and an integer sum do not depend on the order, so the results are the same run to run.
-#include "common.h"
+#include "geglu_stream.h"
 #include "../../include/sdmoe.h"
 
 namespace {
@@ -28,13 +29,13 @@ __global__ __launch_bounds__(256) void expert_stats_kernel(const half_t* __restr
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int e = blockIdx.x * 64 + lane;
   const int slab = blockIdx.y;
-  const int img = slab / spi;
-  const int p0 = (slab - img * spi) * slab_rows, p1 = min(rpi, p0 + slab_rows);
+  const Slab sl = slab_decode(slab, rpi, spi, slab_rows);
+  const int p0 = sl.p0, p1 = sl.p1;
   const int words = (E + 31) >> 5;
   half_t mx = (half_t)(-__builtin_huge_valf());
   int cnt = 0;
   if (e < E) {
-    const long row0 = (long)img * rpi;
+    const long row0 = (long)sl.img * rpi;
     if (pmax) {
       const half_t* col = S + row0 * lds + e;
       for (int p = p0 + wave; p < p1; p += 4) {
@@ -78,18 +79,13 @@ __global__ __launch_bounds__(256) void expert_stats_combine_kernel(const half_t*
   half_t mx = (half_t)(-__builtin_huge_valf());
   int cnt = 0;
   if (e < E) {
-    if (y < nmax) {
-      for (int img = 0; img < nimg; ++img) {
-        if ((img_group ? img_group[img] : 0) != y) continue;
-        for (int s = img * spi + wave; s < (img + 1) * spi; s += 4) {
-          const half_t v = pmax[(long)s * E + e];
-          mx = v > mx ? v : mx;
-        }
-      }
-    } else {
-      const int img = y - nmax;
-      for (int s = img * spi + wave; s < (img + 1) * spi; s += 4) cnt += pcnt[(long)s * E + e];
-    }
+    if (y < nmax)
+      for_group_slabs(img_group, nimg, spi, y, wave, [&](int s) {
+        const half_t v = pmax[(long)s * E + e];
+        mx = v > mx ? v : mx;
+      });
+    else
+      for_image_slabs(y - nmax, spi, wave, [&](int s) { cnt += pcnt[(long)s * E + e]; });
   }
   if (wave > 0) {
     redm[wave - 1][lane] = mx;
@@ -122,27 +118,22 @@ extern "C" int sdmoe_expert_stats(const void* score, long ld_score, const unsign
   if (rows_per_img < 0 || M % rpi) return SDMOE_EARG;
   if (!colmax && !count) return SDMOE_OK;
   if (!workspace) return SDMOE_EARG;
-  const int nimg = M / rpi;
   const int xblocks = (E + 63) / 64;
-  // the largest of the 256-, 64- and 16-row slabs that still gives every CU a block (the bound is the 16-row one
-  // whichever is taken); counts first (int32), then the fp16 maxima, two per workspace float
-  int slab_rows = 256;
-  while (slab_rows > STATS_SLAB_MIN && (long)nimg * ((rpi + slab_rows - 1) / slab_rows) * xblocks < 256)
-    slab_rows /= 4;
-  const int spi = (rpi + slab_rows - 1) / slab_rows;
-  const long nslab = (long)nimg * spi;
-  const long cells = (long)nimg * ((rpi + STATS_SLAB_MIN - 1) / STATS_SLAB_MIN) * E;
+  // the largest slab that still gives every CU a block; counts first (int32), then the fp16 maxima, two per workspace
+  // float
+  const SlabPlan p = slab_plan(M, rows_per_img, xblocks, STATS_SLAB_MIN, 256);
+  const long cells = slab_cells(p, STATS_SLAB_MIN, E);
   const long cnt_floats = count ? cells : 0;
   if (cnt_floats + (colmax ? (cells + 1) / 2 : 0) > workspace_floats) return SDMOE_ESHAPE;
-  const long ny = (colmax ? (long)ngroups : 0) + (count ? (long)nimg : 0);
-  if (nslab > 65535 || ny > 65535) return SDMOE_ESHAPE;
+  const long ny = (colmax ? (long)ngroups : 0) + (count ? (long)p.nimg : 0);
+  if (p.nslab > 65535 || ny > 65535) return SDMOE_ESHAPE;
   hipStream_t s = (hipStream_t)stream;
   int* pcnt = count ? (int*)workspace : nullptr;
   half_t* pmax = colmax ? (half_t*)(workspace + cnt_floats) : nullptr;
-  expert_stats_kernel<<<dim3(xblocks, (unsigned)nslab), 256, 0, s>>>((const half_t*)score, ld_score, sel, E, rpi, spi,
-                                                                     slab_rows, pmax, pcnt);
+  expert_stats_kernel<<<dim3(xblocks, (unsigned)p.nslab), 256, 0, s>>>((const half_t*)score, ld_score, sel, E, p.rpi,
+                                                                       p.spi, p.slab_rows, pmax, pcnt);
   SDMOE_CHECK_LAUNCH();
-  expert_stats_combine_kernel<<<dim3(xblocks, (unsigned)ny), 256, 0, s>>>(pmax, pcnt, nimg, spi, E, img_group,
+  expert_stats_combine_kernel<<<dim3(xblocks, (unsigned)ny), 256, 0, s>>>(pmax, pcnt, p.nimg, p.spi, E, img_group,
                                                                           colmax ? ngroups : 0, (half_t*)colmax, count);
   SDMOE_CHECK_LAUNCH();
   return SDMOE_OK;

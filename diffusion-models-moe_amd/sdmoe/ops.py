@@ -854,6 +854,47 @@ def position_bits(positions, rows_per_img: int, device) -> torch.Tensor:
     return torch.from_numpy(words.copy()).to(device)
 
 
+def _geglu_seam(fn, y, act, out, gate_out):
+    """The operands of a streaming pass over the GEGLU seam y = proj(x) [M, 2F] (geglu_neurons, geglu_sparsity): loads
+    the library and the GELU table, allocates out [M, F] when None and checks the shapes of out and gate_out. Returns
+    (lib, M, F, out, (y pointer, ldy), (out pointer, ldo), (gate_out pointer or None, ldg))."""
+    lib = _lib.load()
+    if act == ACT_GELU:
+        ensure_gelu_table(y.device)
+    yl = _rows(y, "y")
+    M = y.shape[0]
+    F = y.shape[1] // 2
+    if out is None:
+        out = torch.empty((M, F), dtype=torch.float16, device=y.device)
+    ol = _rows(out, "out")
+    if tuple(out.shape) != (M, F):
+        raise ValueError(f"{fn}: out {tuple(out.shape)} is not {(M, F)}")
+    gl = (None, 0) if gate_out is None else _rows(gate_out, "gate_out")
+    if gate_out is not None and tuple(gate_out.shape) != (M, F):
+        raise ValueError(f"{fn}: gate_out {tuple(gate_out.shape)} is not {(M, F)}")
+    return lib, M, F, out, yl, ol, gl
+
+
+def _image_groups(fn, M, rows_per_img, img_group, one=1):
+    """M rows as images of rows_per_img rows (0: `one` image) with an optional group table: (rows_per_img as an int,
+    images, img_group pointer or None). The table's length is checked where the rows divide into images; where they do
+    not, the entry point refuses the call."""
+    rpi = int(rows_per_img)
+    divides = rpi <= 0 or M % rpi == 0
+    nimg = M // rpi if rpi > 0 and divides else one
+    if img_group is None:
+        return rpi, nimg, None
+    if divides and img_group.numel() != nimg:
+        raise ValueError(f"{fn}: img_group has {img_group.numel()} entries for {nimg} images")
+    return rpi, nimg, _dev(img_group, "img_group", torch.int32)
+
+
+def _ws_args(device, workspace):
+    """(pointer, floats) of the fp32 scratch of a statistics pass: `workspace`, or the device's shared one."""
+    ws = _workspace(device) if workspace is None else workspace
+    return _dev(ws, "workspace", torch.float32), ws.numel()
+
+
 def geglu_neurons(y, act=ACT_GELU, *, override_bits=None, override_value=0.0, gate_out=None, rows_per_img=0,
                   img_group=None, ngroups=1, pos_bits=None, colmax=None, out=None, workspace=None):
     """Dense GEGLU over y = proj(x) [M, 2F] with a per-neuron gate override and a per-group column maximum
@@ -863,43 +904,24 @@ def geglu_neurons(y, act=ACT_GELU, *, override_bits=None, override_value=0.0, ga
     group img_group[i], int32 device [M / rows_per_img]; None = all group 0), restricted to the positions of pos_bits
     (int32 [ceil(rows_per_img / 32)], position_bits) when given. workspace: fp32 scratch for the per-slab partial
     maxima (default: the device's shared workspace). Returns out."""
-    lib = _lib.load()
-    if act == ACT_GELU:
-        ensure_gelu_table(y.device)
-    yp, ldy = _rows(y, "y")
-    M = y.shape[0]
-    F = y.shape[1] // 2
-    if out is None:
-        out = torch.empty((M, F), dtype=torch.float16, device=y.device)
-    op, ldo = _rows(out, "out")
-    if tuple(out.shape) != (M, F):
-        raise ValueError(f"geglu_neurons: out {tuple(out.shape)} is not {(M, F)}")
-    gp, ldg = (None, 0) if gate_out is None else _rows(gate_out, "gate_out")
-    if gate_out is not None and tuple(gate_out.shape) != (M, F):
-        raise ValueError(f"geglu_neurons: gate_out {tuple(gate_out.shape)} is not {(M, F)}")
-    rpi = int(rows_per_img)
-    nimg = M // rpi if rpi > 0 and M % rpi == 0 else 1
+    lib, M, F, out, (yp, ldy), (op, ldo), (gp, ldg) = _geglu_seam("geglu_neurons", y, act, out, gate_out)
     obp = None
     if override_bits is not None:
         if override_bits.numel() * 32 != F:
             raise ValueError(f"geglu_neurons: {override_bits.numel()} override words for F={F}")
         obp = _dev(override_bits, "override_bits", torch.int32)
-    cp = igp = pbp = None
+    cp = pbp = None
     if colmax is not None:
         if tuple(colmax.shape) != (int(ngroups), F):
             raise ValueError(f"geglu_neurons: colmax {tuple(colmax.shape)} is not {(int(ngroups), F)}")
         cp = _dev(colmax, "colmax")
-        if img_group is not None:
-            if (rpi <= 0 or M % rpi == 0) and img_group.numel() != nimg:
-                raise ValueError(f"geglu_neurons: img_group has {img_group.numel()} entries for {nimg} images")
-            igp = _dev(img_group, "img_group", torch.int32)
-        if pos_bits is not None:
-            if pos_bits.numel() != -(-(rpi if rpi > 0 else M) // 32):
-                raise ValueError(f"geglu_neurons: {pos_bits.numel()} pos_bits words for {rpi if rpi > 0 else M} rows")
-            pbp = _dev(pos_bits, "pos_bits", torch.int32)
-    ws = _workspace(y.device) if workspace is None else workspace
+    rpi, _, igp = _image_groups("geglu_neurons", M, rows_per_img, img_group if colmax is not None else None)
+    if colmax is not None and pos_bits is not None:
+        if pos_bits.numel() != -(-(rpi if rpi > 0 else M) // 32):
+            raise ValueError(f"geglu_neurons: {pos_bits.numel()} pos_bits words for {rpi if rpi > 0 else M} rows")
+        pbp = _dev(pos_bits, "pos_bits", torch.int32)
     st = lib.sdmoe_geglu_neurons(yp, ldy, M, F, act, obp, float(override_value), op, ldo, gp, ldg, rpi, igp,
-                                 int(ngroups), pbp, cp, _dev(ws, "workspace", torch.float32), ws.numel(), _stream())
+                                 int(ngroups), pbp, cp, *_ws_args(y.device, workspace), _stream())
     _lib.check(st, "sdmoe_geglu_neurons")
     return out
 
@@ -914,24 +936,9 @@ def geglu_sparsity(y, act=ACT_GELU, *, threshold=0.0, rows_per_img=0, img_group=
     [ngroups, 2]) their sums over the neurons. Either totals or both arrays must be given; every given buffer is
     written in full (none needs zeroing). gate_out (optional [M, F]) receives g. workspace: fp32 scratch for the
     per-slab partial counts (default: the device's shared workspace). Returns out."""
-    lib = _lib.load()
-    if act == ACT_GELU:
-        ensure_gelu_table(y.device)
-    yp, ldy = _rows(y, "y")
-    M = y.shape[0]
-    F = y.shape[1] // 2
-    if out is None:
-        out = torch.empty((M, F), dtype=torch.float16, device=y.device)
-    op, ldo = _rows(out, "out")
-    if tuple(out.shape) != (M, F):
-        raise ValueError(f"geglu_sparsity: out {tuple(out.shape)} is not {(M, F)}")
-    gp, ldg = (None, 0) if gate_out is None else _rows(gate_out, "gate_out")
-    if gate_out is not None and tuple(gate_out.shape) != (M, F):
-        raise ValueError(f"geglu_sparsity: gate_out {tuple(gate_out.shape)} is not {(M, F)}")
+    lib, M, F, out, (yp, ldy), (op, ldo), (gp, ldg) = _geglu_seam("geglu_sparsity", y, act, out, gate_out)
     if totals is None and (col_zero is None or col_neg is None):
         raise ValueError("geglu_sparsity: give totals, or both col_zero and col_neg")
-    rpi = int(rows_per_img)
-    nimg = M // rpi if rpi > 0 and M % rpi == 0 else 1
     ptrs = {}
     for name, t, shape, dtype in (("col_zero", col_zero, (int(ngroups), F), torch.int32),
                                   ("col_neg", col_neg, (int(ngroups), F), torch.int32),
@@ -939,15 +946,10 @@ def geglu_sparsity(y, act=ACT_GELU, *, threshold=0.0, rows_per_img=0, img_group=
         if t is not None and tuple(t.shape) != shape:
             raise ValueError(f"geglu_sparsity: {name} {tuple(t.shape)} is not {shape}")
         ptrs[name] = None if t is None else _dev(t, name, dtype)
-    igp = None
-    if img_group is not None:
-        if (rpi <= 0 or M % rpi == 0) and img_group.numel() != nimg:
-            raise ValueError(f"geglu_sparsity: img_group has {img_group.numel()} entries for {nimg} images")
-        igp = _dev(img_group, "img_group", torch.int32)
-    ws = _workspace(y.device) if workspace is None else workspace
+    rpi, _, igp = _image_groups("geglu_sparsity", M, rows_per_img, img_group)
     st = lib.sdmoe_geglu_sparsity(yp, ldy, M, F, act, float(threshold), op, ldo, gp, ldg, rpi, igp, int(ngroups),
                                   ptrs["col_zero"], ptrs["col_neg"], ptrs["totals"],
-                                  _dev(ws, "workspace", torch.float32), ws.numel(), _stream())
+                                  *_ws_args(y.device, workspace), _stream())
     _lib.check(st, "sdmoe_geglu_sparsity")
     return out
 
@@ -1043,11 +1045,9 @@ def expert_stats(score, *, sel=None, rows_per_img=0, img_group=None, ngroups=1, 
     lib = _lib.load()
     sp, lds = _rows(score, "score")
     M, E = score.shape
-    rpi = int(rows_per_img)
-    if rpi < 0:
-        raise ValueError(f"expert_stats: rows_per_img = {rpi}")
-    nimg = M // rpi if rpi > 0 and M % rpi == 0 else min(M, 1)
-    selp = cp = cntp = igp = None
+    if int(rows_per_img) < 0:
+        raise ValueError(f"expert_stats: rows_per_img = {int(rows_per_img)}")
+    selp = cp = cntp = None
     if sel is not None:
         if tuple(sel.shape) != (M, (E + 31) // 32):
             raise ValueError(f"expert_stats: sel {tuple(sel.shape)} is not {(M, (E + 31) // 32)}")
@@ -1056,17 +1056,14 @@ def expert_stats(score, *, sel=None, rows_per_img=0, img_group=None, ngroups=1, 
         if tuple(colmax.shape) != (int(ngroups), E):
             raise ValueError(f"expert_stats: colmax {tuple(colmax.shape)} is not {(int(ngroups), E)}")
         cp = _dev(colmax, "colmax")
-        if img_group is not None:
-            if (rpi <= 0 or M % rpi == 0) and img_group.numel() != nimg:
-                raise ValueError(f"expert_stats: img_group has {img_group.numel()} entries for {nimg} images")
-            igp = _dev(img_group, "img_group", torch.int32)
+    rpi, nimg, igp = _image_groups("expert_stats", M, rows_per_img, img_group if colmax is not None else None,
+                                   one=min(M, 1))
     if count is not None:
         if (rpi <= 0 or M % rpi == 0) and tuple(count.shape) != (nimg, E):
             raise ValueError(f"expert_stats: count {tuple(count.shape)} is not {(nimg, E)}")
         cntp = _dev(count, "count", torch.int32)
-    ws = _workspace(score.device) if workspace is None else workspace
     st = lib.sdmoe_expert_stats(sp, lds, selp, M, E, rpi, igp, int(ngroups), cp, cntp,
-                                _dev(ws, "workspace", torch.float32), ws.numel(), _stream())
+                                *_ws_args(score.device, workspace), _stream())
     _lib.check(st, "sdmoe_expert_stats")
     return colmax, count
 

@@ -277,14 +277,11 @@ class GEGLU(nn.Module):
             out = ops.geglu_route(self.proj.run(x2), None, act)
         return out.view(*shp[:-1], self.inner_dim)
 
-    def neurons(self, x, override_bits=None, override_value=0.0, want_gate=False, colmax=None, img_group=None,
-                ngroups=1, pos_bits=None):
-        """proj GEMM + the neuron-level streaming pass (ops.geglu_neurons), ignoring any MoE routing: value * g' in the
-        natural neuron order, g' = act(gate) with the neurons of override_bits set to override_value
-        (RemoveNeurons, neuron_receivers/remove_skilled_neurons.py:26-42); colmax ([ngroups, 4C] fp16, optional)
-        receives the per-group maximum of act(gate) over the tokens (pos_bits: only those positions) of the images
-        x[i] of each group (NeuronPredictivity, predictivity.py:42-53). x: [images, tokens, C] (or [tokens, C]: one
-        image). Returns (out, g' or None)."""
+    def _seam_operands(self, x, want_gate):
+        """What neurons() and sparsity() hand to their streaming pass over the seam: (y = proj(LN(x)) [tokens, 8C] in
+        the natural neuron order, the rows per image of x, an empty gate buffer [tokens, 4C] or None, view), where
+        view(t) gives a [tokens, 4C] result (or None) the leading dimensions of x. Clears what the last routed() call
+        recorded for the down projection."""
         shp = x.shape
         x2 = x.reshape(-1, shp[-1])
         norm = self._take_ln(x)
@@ -294,11 +291,25 @@ class GEGLU(nn.Module):
         self._out_keep = None
         y = self.proj.run(x2)
         gate = torch.empty((x2.shape[0], self.inner_dim), dtype=torch.float16, device=x.device) if want_gate else None
+
+        def view(t):
+            return None if t is None else t.view(*shp[:-1], self.inner_dim)
+
+        return y, (shp[-2] if x.dim() >= 3 else 0), gate, view
+
+    def neurons(self, x, override_bits=None, override_value=0.0, want_gate=False, colmax=None, img_group=None,
+                ngroups=1, pos_bits=None):
+        """proj GEMM + the neuron-level streaming pass (ops.geglu_neurons), ignoring any MoE routing: value * g' in the
+        natural neuron order, g' = act(gate) with the neurons of override_bits set to override_value
+        (RemoveNeurons, neuron_receivers/remove_skilled_neurons.py:26-42); colmax ([ngroups, 4C] fp16, optional)
+        receives the per-group maximum of act(gate) over the tokens (pos_bits: only those positions) of the images
+        x[i] of each group (NeuronPredictivity, predictivity.py:42-53). x: [images, tokens, C] (or [tokens, C]: one
+        image). Returns (out, g' or None)."""
+        y, rpi, gate, view = self._seam_operands(x, want_gate)
         out = ops.geglu_neurons(y, act_code(self.gelu), override_bits=override_bits, override_value=override_value,
-                                gate_out=gate, rows_per_img=shp[-2] if x.dim() >= 3 else 0, img_group=img_group,
-                                ngroups=ngroups, pos_bits=pos_bits, colmax=colmax)
-        out = out.view(*shp[:-1], self.inner_dim)
-        return out, (gate.view(*shp[:-1], self.inner_dim) if want_gate else None)
+                                gate_out=gate, rows_per_img=rpi, img_group=img_group, ngroups=ngroups,
+                                pos_bits=pos_bits, colmax=colmax)
+        return view(out), view(gate)
 
     def sparsity(self, x, threshold=0.0, col_zero=None, col_neg=None, totals=None, img_group=None, ngroups=1,
                  want_gate=False):
@@ -309,20 +320,10 @@ class GEGLU(nn.Module):
         (SparsityMeasure, neuron_receivers/sparsity_measure.py:13-18 with the counting of sparsity/
         check_sparsity.py:41-46 done on the device). x: [images, tokens, C] (or [tokens, C]: one image). Returns
         (out, act(gate) or None)."""
-        shp = x.shape
-        x2 = x.reshape(-1, shp[-1])
-        norm = self._take_ln(x)
-        if norm is not None:
-            x2 = ops.layernorm(x2, norm.weight, norm.bias, norm.eps)
-        self._out_perm = None
-        self._out_keep = None
-        y = self.proj.run(x2)
-        gate = torch.empty((x2.shape[0], self.inner_dim), dtype=torch.float16, device=x.device) if want_gate else None
-        out = ops.geglu_sparsity(y, act_code(self.gelu), threshold=threshold,
-                                 rows_per_img=shp[-2] if x.dim() >= 3 else 0, img_group=img_group, ngroups=ngroups,
-                                 col_zero=col_zero, col_neg=col_neg, totals=totals, gate_out=gate)
-        out = out.view(*shp[:-1], self.inner_dim)
-        return out, (gate.view(*shp[:-1], self.inner_dim) if want_gate else None)
+        y, rpi, gate, view = self._seam_operands(x, want_gate)
+        out = ops.geglu_sparsity(y, act_code(self.gelu), threshold=threshold, rows_per_img=rpi, img_group=img_group,
+                                 ngroups=ngroups, col_zero=col_zero, col_neg=col_neg, totals=totals, gate_out=gate)
+        return view(out), view(gate)
 
     def forward(self, x, scale=1.0):
         if self._sdmoe_deferred and self._forward_hooks:

@@ -31,10 +31,19 @@ ROWS = [(64, 4), (100, 4), (1024, 4), (64, 2), (100, 2), (1024, 2)]  # (rows per
 
 
 def grouping(nimg):
-    """4 images: groups [0, 1, 0, 1]; 2 images: img_group None (one group)."""
-    if nimg == 4:
-        return [0, 1, 0, 1], 2, torch.tensor([0, 1, 0, 1], dtype=torch.int32, device=DEV)
-    return [0] * nimg, 1, None
+    """2 images: img_group None (one group); 4 or 32 images: image i in group i % 2."""
+    if nimg == 2:
+        return [0, 0], 1, None
+    groups = [i % 2 for i in range(nimg)]
+    return groups, 2, torch.tensor(groups, dtype=torch.int32, device=DEV)
+
+
+def row_cases(Es):
+    """ROWS at every E (ids as a stacked parametrize gives them), then 32 images of 300 rows at E = 256: 32 x 2 x 4 =
+    256 blocks, the least that takes 256-row slabs, with a 44-row second slab. ROWS reaches the 16-row slabs, and the
+    64-row ones only at (1024, 4) with E = 256."""
+    return [pytest.param(rpi, nimg, E, id=f"{rpi}-{nimg}-{E}") for E in Es for rpi, nimg in ROWS + [(300, 32)]
+            if rpi != 300 or E == 256]
 
 
 # ------------------------------------------------------------------------------------------------ kernel
@@ -71,11 +80,10 @@ def group_amax(score, rpi, groups, ngroups):
                         for g in range(ngroups)])
 
 
-@pytest.mark.parametrize("E", [64, 256, 40])
-@pytest.mark.parametrize("rpi,nimg", ROWS)
+@pytest.mark.parametrize("rpi,nimg,E", row_cases([64, 256, 40]))
 def test_column_maximum(rpi, nimg, E):
     """rpi = 100 leaves a partial slab, 1024 gives several slabs per image; the always-negative columns fail a
-    zero-initialised maximum."""
+    zero-initialised maximum. (300, 32) at E = 256 runs 256-row slabs (row_cases), the 32 images in two groups."""
     score = score_case(nimg * rpi, E)
     assert score.stride(0) > E
     groups, ng, table = grouping(nimg)
@@ -85,9 +93,9 @@ def test_column_maximum(rpi, nimg, E):
     assert bool((colmax[:, ::7] < 0).all())
 
 
-@pytest.mark.parametrize("E", [64, 40, 100, 256])
-@pytest.mark.parametrize("rpi,nimg", ROWS)
+@pytest.mark.parametrize("rpi,nimg,E", row_cases([64, 40, 100, 256]))
 def test_selection_counts(rpi, nimg, E):
+    """(300, 32) at E = 256 runs 256-row slabs (row_cases): the counts of a 256-row and of a 44-row slab per image."""
     M = nimg * rpi
     sel, on = sel_case(M, E)
     count = torch.full((nimg, E), -1, dtype=torch.int32, device=DEV)

@@ -74,14 +74,18 @@ def amax_rows(gate, rpi, groups, ngroups, positions=None):
 
 
 @pytest.mark.parametrize("act", ["gelu", "relu"])
-@pytest.mark.parametrize("rpi,nimg", [(64, 4), (256, 4), (1024, 4), (100, 4), (64, 2), (1024, 2), (100, 2)])
-def test_column_maximum(rpi, nimg, act):
-    """nimg = 4: groups [0, 1, 0, 1]; nimg = 2: img_group None (one group). rpi = 100 leaves a partial slab, 1024 gives
-    several slabs per image; the always-negative columns fail a zero-initialised maximum."""
-    F = 1280
+@pytest.mark.parametrize("rpi,nimg,F", [pytest.param(rpi, nimg, 1280, id=f"{rpi}-{nimg}") for rpi, nimg in
+                                        [(64, 4), (256, 4), (1024, 4), (100, 4), (64, 2), (1024, 2), (100, 2)]]
+                         + [pytest.param(300, 128, 544, id="300-128-544")])
+def test_column_maximum(rpi, nimg, F, act):
+    """nimg = 2: img_group None (one group); otherwise image i is in group i % 2. rpi = 100 leaves a partial slab, 1024
+    gives several slabs per image; the always-negative columns fail a zero-initialised maximum. Every F = 1280 shape
+    runs 64-row slabs (at most 48 blocks of 256 rows). 128 images of 300 rows at F = 544 reach the 256-row slabs:
+    128 x 2 x 2 = 512 blocks, the least that takes them, with a 44-row second slab and a partial column block (the
+    input of test_gpu_sparsity.test_counts_256_row_slabs)."""
     y, ref, gref = case(nimg * rpi, F, act)
-    groups, ng = ([0, 1, 0, 1], 2) if nimg == 4 else ([0, 0], 1)
-    table = torch.tensor(groups, dtype=torch.int32, device=DEV) if nimg == 4 else None
+    groups, ng = ([i % 2 for i in range(nimg)], 2) if nimg != 2 else ([0, 0], 1)
+    table = torch.tensor(groups, dtype=torch.int32, device=DEV) if nimg != 2 else None
     colmax = torch.full((ng, F), 7.0, dtype=torch.float16, device=DEV)
     out = ops.geglu_neurons(y, ACTS[act], rows_per_img=rpi, img_group=table, ngroups=ng, colmax=colmax)
     want = amax_rows(gref, rpi, groups, ng)
@@ -92,6 +96,8 @@ def test_column_maximum(rpi, nimg, act):
 
 
 def box_lists(rpi):
+    if rpi == 300:
+        return [[256, 270, 299]]  # wholly in the second, 44-row slab of each image: the first contributes nothing
     lists = [[0], [rpi - 1], [0, 3, 5, 17, 31]]
     if rpi == 1024:
         lists.append([1, 40, 63])  # confined to the image's first slab: the others contribute nothing
@@ -99,9 +105,12 @@ def box_lists(rpi):
 
 
 @pytest.mark.parametrize("act", ["gelu", "relu"])
-@pytest.mark.parametrize("rpi", [64, 1024])
+@pytest.mark.parametrize("rpi", [64, 1024, 300])
 def test_bounding_box_positions(rpi, act):
-    F, nimg, groups = 320, 4, [0, 1, 0, 1]
+    """rpi = 64 and 1024: 4 images at F = 320, 64-row slabs. rpi = 300: the 128 images at F = 544 of
+    test_column_maximum, 256-row slabs (512 blocks), image i in group i % 2."""
+    F, nimg = (544, 128) if rpi == 300 else (320, 4)
+    groups = [i % 2 for i in range(nimg)]
     y, ref, gref = case(nimg * rpi, F, act)
     table = torch.tensor(groups, dtype=torch.int32, device=DEV)
     for pos in box_lists(rpi):

@@ -12,6 +12,7 @@ for f in "$R"/diffusion-models-moe_amd/csrc/*.hip; do
   if cmp -s "$f" "$T/diffusion-models-moe_amd/csrc/$b.hip" && cmp -s "$R/include/sdmoe.h" "$T/include/sdmoe.h" \
      && cmp -s "$R/diffusion-models-moe_amd/csrc/common.h" "$T/diffusion-models-moe_amd/csrc/common.h" \
      && cmp -s "$R/diffusion-models-moe_amd/csrc/tune.h" "$T/diffusion-models-moe_amd/csrc/tune.h" \
+     && cmp -s "$R/diffusion-models-moe_amd/csrc/geglu_stream.h" "$T/diffusion-models-moe_amd/csrc/geglu_stream.h" 2>/dev/null \
      && { [ "$b" != gemm ] || cmp -s "$R/diffusion-models-moe_amd/csrc/gemm_kernel.h" "$T/diffusion-models-moe_amd/csrc/gemm_kernel.h" 2>/dev/null; } \
      && [ -f "$R/diffusion-models-moe_amd/csrc/build/$b.o" ]; then
     cp "$R/diffusion-models-moe_amd/csrc/build/$b.o" "$T/diffusion-models-moe_amd/csrc/build/"
