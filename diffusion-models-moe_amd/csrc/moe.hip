@@ -25,6 +25,7 @@ struct RouteParams {
   const int* e_off;         // [E+1] CSR offsets into e_nid
   const int* e_nid;         // [F] neuron ids grouped by expert, ascending within an expert
   const uint32_t* removed;  // [ceil(E/32)] or null
+  const half_t* bias;       // [E] or null: added to the fp16 score (sdmoe_geglu_route_bias)
   half_t* out; long ldo;
   half_t* gate_out; long ldg;
   uint32_t* sel_out;        // [M][ceil(E/32)] or null (top-k result, before the removal mask)
@@ -77,6 +78,7 @@ __global__ __launch_bounds__(256) void geglu_route_kernel(RouteParams p) {
         for (int j = j0; j < j1; ++j) acc += (float)gact[p.e_nid[j]];
         sc = (half_t)acc;
         if (p.removed && ((p.removed[e >> 5] >> (e & 31)) & 1u)) sc = (half_t)0.f;
+        if (p.bias) sc = (half_t)((float)sc + (float)p.bias[e]);  // exact fp32 sum, one rounding: the fp16 add
         if (p.score_out && live) p.score_out[(long)m * p.E + e] = sc;
       }
       key[i] = valid[i] ? order_key(sc) : 0u;
@@ -569,10 +571,10 @@ extern "C" int sdmoe_moe_topk_keep(int M, int F, int E, int esize, int k, const 
                            sel_out, (unsigned long long*)keep, (hipStream_t)stream);
 }
 
-extern "C" int sdmoe_geglu_route(const void* Y, long ldy, int M, int F, int E, int k, int act, const int* labels,
-                                 const int* e_off, const int* e_nid, const unsigned* removed_bits, void* out,
-                                 long ldo, void* gate_out, long ldg, unsigned* sel_out, void* score_out,
-                                 void* stream) {
+extern "C" int sdmoe_geglu_route_bias(const void* Y, long ldy, int M, int F, int E, int k, int act,
+                                      const int* labels, const int* e_off, const int* e_nid,
+                                      const unsigned* removed_bits, void* out, long ldo, void* gate_out, long ldg,
+                                      unsigned* sel_out, void* score_out, const void* bias, void* stream) {
   if (M == 0) return SDMOE_OK;
   if (!Y || !out || M < 0 || F <= 0 || E < 0) return SDMOE_EARG;
   if (F % 8 || ldy % 8 || ldo % 8 || (gate_out && ldg % 8)) return SDMOE_ESHAPE;
@@ -580,7 +582,7 @@ extern "C" int sdmoe_geglu_route(const void* Y, long ldy, int M, int F, int E, i
   if (E > 0 && (!labels || !e_off || !e_nid || k < 0 || k > E)) return SDMOE_EARG;
   if (!(act == ACT_GELU || act == ACT_RELU || act == ACT_NONE || act == ACT_SILU)) return SDMOE_EUNSUP;
   RouteParams p{(const half_t*)Y, ldy, M, F, E, k, act, labels, e_off, e_nid, removed_bits,
-                (half_t*)out, ldo, (half_t*)gate_out, ldg, sel_out, (half_t*)score_out,
+                (const half_t*)bias, (half_t*)out, ldo, (half_t*)gate_out, ldg, sel_out, (half_t*)score_out,
                 act == ACT_GELU ? sdmoe_gelu_tab_current() : nullptr};
   const size_t smem = (size_t)4 * F * sizeof(half_t) + 4 * 8 * sizeof(uint32_t);
   if (smem > 160 * 1024) return SDMOE_ESHAPE;
@@ -591,4 +593,12 @@ extern "C" int sdmoe_geglu_route(const void* Y, long ldy, int M, int F, int E, i
   else geglu_route_kernel<4><<<blocks, 256, smem, s>>>(p);
   SDMOE_CHECK_LAUNCH();
   return SDMOE_OK;
+}
+
+extern "C" int sdmoe_geglu_route(const void* Y, long ldy, int M, int F, int E, int k, int act, const int* labels,
+                                 const int* e_off, const int* e_nid, const unsigned* removed_bits, void* out,
+                                 long ldo, void* gate_out, long ldg, unsigned* sel_out, void* score_out,
+                                 void* stream) {
+  return sdmoe_geglu_route_bias(Y, ldy, M, F, E, k, act, labels, e_off, e_nid, removed_bits, out, ldo, gate_out, ldg,
+                                sel_out, score_out, nullptr, stream);
 }

@@ -8,8 +8,8 @@ maximum routing scores -> paired t-test -> expert lists) and
 selection histogram for choosing topk_experts, and SparsityMeasure, the gate-sparsity counts of a relufied U-Net (the
 measurement behind sparsity/check_sparsity.py's sparsity.json); the HPO path (BaseUNetReceiver, RemoveNeuronsHPO,
 RemoveNeuronsNoiseHPO: the receivers modularity/remove_experts_hpo.py and remove_experts_noise_hpo.py drive, the noise
-objective computed on the device by sdmoe_noise_distance) and SaveStates. The one remaining receiver of the reference,
-AddExperts, is not exported.
+objective computed on the device by sdmoe_noise_distance), SaveStates, and AddExperts, the counterpart
+of RemoveExperts: a per-expert score bias ahead of a top-k at int(0.8 k).
 """
 from neuron_receivers.base_receiver import BaseNeuronReceiver, GEGLU, GELU  # noqa: F401
 from neuron_receivers.predictivity import NeuronPredictivity  # noqa: F401
@@ -17,6 +17,7 @@ from neuron_receivers.neuron_predictivity_bb import NeuronPredictivityBB  # noqa
 from neuron_receivers.remove_skilled_neurons import RemoveNeurons  # noqa: F401
 from neuron_receivers.moefy import MOEFy  # noqa: F401
 from neuron_receivers.remove_skilled_experts import RemoveExperts  # noqa: F401
+from neuron_receivers.add_skilled_experts import AddExperts  # noqa: F401
 from neuron_receivers.remove_wanda_neurons_fast import WandaRemoveNeuronsFast  # noqa: F401
 from neuron_receivers.remove_wanda_per_prompt import WandaRemovePerPrompt  # noqa: F401
 from neuron_receivers.multi_concept_remover import MultiConceptRemoverWanda  # noqa: F401

@@ -37,6 +37,8 @@ SIGNATURES = {
     "sdmoe_linear_geglu_ln": [_P, _L, _P, _L, _P, _P, _F, _P, _L, _I, _I, _I, _I, _P, _L, _I, _P],
     "sdmoe_attention": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "sdmoe_geglu_route": [_P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P],
+    "sdmoe_score_bias": [_P, _L, _I, _I, _P, _P, _L, _P],
+    "sdmoe_geglu_route_bias": [_P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P],
     "sdmoe_linear_geglu": [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _P, _L, _I, _P],
     "sdmoe_moe_topk_mask": [_P, _L, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P],
     "sdmoe_moe_topk_keep": [_I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P],

@@ -742,20 +742,21 @@ def linear_geglu(x, w_il, b_il, act=ACT_GELU, *, score=None, esize=0, out=None, 
     return out
 
 
-def moe_topk_mask(P, score, routing: "Routing", removed=None, sel_out=None):
-    """In place on the fused product P [M, F]: zero the neurons of experts outside each token's top-k."""
+def moe_topk_mask(P, score, routing: "Routing", removed=None, sel_out=None, k=None):
+    """In place on the fused product P [M, F]: zero the neurons of experts outside each token's top-k. k overrides
+    routing.k."""
     lib = _lib.load()
     pp, ldp = _rows(P, "P")
     sp, lds = _rows(score, "score")
-    st = lib.sdmoe_moe_topk_mask(pp, ldp, P.shape[0], P.shape[1], routing.E, routing.esize, routing.k, sp, lds,
-                                 _ptr(removed), _ptr(sel_out), _stream())
+    st = lib.sdmoe_moe_topk_mask(pp, ldp, P.shape[0], P.shape[1], routing.E, routing.esize,
+                                 routing.k if k is None else int(k), sp, lds, _ptr(removed), _ptr(sel_out), _stream())
     _lib.check(st, "sdmoe_moe_topk_mask")
     return P
 
 
-def moe_topk_keep(score, routing: "Routing", M: int, removed=None, sel_out=None, keep=None):
+def moe_topk_keep(score, routing: "Routing", M: int, removed=None, sel_out=None, keep=None, k=None):
     """Top-k selection of sdmoe_moe_topk_mask as keep bits for sdmoe_linear_keep: int64 [F/64, M] words, bit j of
-    word (s, m) = expert-major neuron 64 s + j of token m kept."""
+    word (s, m) = expert-major neuron 64 s + j of token m kept. k overrides routing.k."""
     lib = _lib.load()
     sp, lds = _rows(score, "score")
     F = routing.E * routing.esize
@@ -763,8 +764,8 @@ def moe_topk_keep(score, routing: "Routing", M: int, removed=None, sel_out=None,
         keep = torch.empty((F // 64, M), dtype=torch.int64, device=score.device)
     if tuple(keep.shape) != (F // 64, M) or keep.dtype != torch.int64:
         raise ValueError(f"keep must be int64 [{F // 64}, {M}], got {keep.dtype} {tuple(keep.shape)}")
-    st = lib.sdmoe_moe_topk_keep(M, F, routing.E, routing.esize, routing.k, sp, lds, _ptr(removed),
-                                 _dev(keep, "keep", torch.int64), _ptr(sel_out), _stream())
+    st = lib.sdmoe_moe_topk_keep(M, F, routing.E, routing.esize, routing.k if k is None else int(k), sp, lds,
+                                 _ptr(removed), _dev(keep, "keep", torch.int64), _ptr(sel_out), _stream())
     _lib.check(st, "sdmoe_moe_topk_keep")
     return keep
 
@@ -804,10 +805,58 @@ def removed_bits(expert_ids, num_experts: int, device) -> torch.Tensor:
     return torch.tensor(words, dtype=torch.int32, device=device)
 
 
+def expert_bias(expert_ids, std, E: int, device, scale=5.0) -> torch.Tensor:
+    """The per-expert score bias of AddExperts (add_skilled_experts.py:55) as fp16 [E] on `device`:
+    scale * torch.tensor(std).to(float16) -- the reference's own torch operations on the CPU, so its two roundings
+    (std to fp16, then the scalar product to fp16) -- at the listed expert ids, +0 elsewhere. A duplicate id is applied
+    once, as the reference's indexed assignment does. Raises IndexError for an id outside [0, E) and, unlike the
+    reference (which would add it to the scores), ValueError when a LISTED expert's std or bias is NaN or infinite
+    (StatMeter writes NaN for a cell it never updated)."""
+    E = int(E)
+    std = [float(v) for v in std]
+    if len(std) != E:
+        raise ValueError(f"expert_bias: std has {len(std)} entries, the module has {E} experts")
+    ids = []
+    for e in expert_ids:
+        e = int(e)
+        if not 0 <= e < E:
+            raise IndexError(f"expert id {e} out of range [0, {E})")
+        ids.append(e)
+    bias = torch.zeros(E, dtype=torch.float16)
+    if ids:
+        idx = torch.tensor(sorted(set(ids)), dtype=torch.int64)
+        std16 = torch.tensor(std).to(torch.float16)
+        listed = (float(scale) * std16)[idx]
+        if not bool(torch.isfinite(std16[idx]).all() and torch.isfinite(listed).all()):
+            bad = [int(e) for e in idx[~(torch.isfinite(std16[idx]) & torch.isfinite(listed))]]
+            raise ValueError(f"expert_bias: std or bias of listed experts {bad} is NaN or infinite")
+        bias[idx] = listed
+    return bias.to(device)
+
+
+def score_bias(score, bias, out=None):
+    """out[m, e] = fp16(score[m, e] + bias[e]) (sdmoe_score_bias): score [M, E] fp16 (a row-strided view is fine),
+    bias fp16 [E] (expert_bias). out None: in place on score. Returns out."""
+    lib = _lib.load()
+    sp, lds = _rows(score, "score")
+    M, E = score.shape
+    if tuple(bias.shape) != (E,):
+        raise ValueError(f"score_bias: bias {tuple(bias.shape)} is not {(E,)}")
+    if out is None:
+        out = score
+    if tuple(out.shape) != (M, E):
+        raise ValueError(f"score_bias: out {tuple(out.shape)} is not {(M, E)}")
+    op, ldo = _rows(out, "out")
+    st = lib.sdmoe_score_bias(sp, lds, M, E, _dev(bias, "bias"), op, ldo, _stream())
+    _lib.check(st, "sdmoe_score_bias")
+    return out
+
+
 def geglu_route(y, routing: Routing | None, act=ACT_GELU, removed=None, out=None, gate_out=None, sel_out=None,
-                score_out=None, k=None):
+                score_out=None, k=None, bias=None):
     """Routed GEGLU over y = proj(x) [M, 2F]; routing None -> dense value*act(gate). k overrides routing.k
-    (k = E: every expert kept, i.e. the dense product plus the per-token expert scores)."""
+    (k = E: every expert kept, i.e. the dense product plus the per-token expert scores). bias (fp16 [E],
+    expert_bias): added to the fp16 expert scores before they are ranked and written (sdmoe_geglu_route_bias)."""
     lib = _lib.load()
     if act == ACT_GELU:
         ensure_gelu_table(y.device)
@@ -825,6 +874,13 @@ def geglu_route(y, routing: Routing | None, act=ACT_GELU, removed=None, out=None
             raise ValueError(f"routing has F={routing.F}, projection gives F={F}")
         E, k = routing.E, (routing.k if k is None else int(k))
         lab, off, nid = routing.labels.data_ptr(), routing.e_off.data_ptr(), routing.e_nid.data_ptr()
+    if bias is not None:
+        if routing is None or tuple(bias.shape) != (E,):
+            raise ValueError(f"geglu_route: bias {tuple(bias.shape)} needs a routing with E = {bias.numel()} experts")
+        st = lib.sdmoe_geglu_route_bias(yp, ldy, M, F, E, k, act, lab, off, nid, _ptr(removed), op, ldo, gp, ldg,
+                                        _ptr(sel_out), _ptr(score_out), _dev(bias, "bias"), _stream())
+        _lib.check(st, "sdmoe_geglu_route_bias")
+        return out
     st = lib.sdmoe_geglu_route(yp, ldy, M, F, E, k, act, lab, off, nid, _ptr(removed), op, ldo, gp, ldg,
                                _ptr(sel_out), _ptr(score_out), _stream())
     _lib.check(st, "sdmoe_geglu_route")

@@ -190,11 +190,14 @@ class GEGLU(nn.Module):
             self._il_ln_key = key
         return self._il_ln
 
-    def routed(self, x, removed=None, want_gate=False, sel_out=None, score_out=None):
+    def routed(self, x, removed=None, want_gate=False, sel_out=None, score_out=None, bias=None, k=None):
         """proj GEMM + routed GEGLU kernel. x: [..., C] fp16. Returns (out [..., 4C], masked gate or None).
         sel_out (optional int32 [tokens, ceil(E/32)]) receives the per-token top-k expert bitmask, score_out
         (optional fp16 [tokens, E]) the expert scores the top-k ranked (removed experts: 0 on the unfused path; their
         raw gate sums on the fused path, where the removal is applied inside the top-k kernel).
+        bias (optional fp16 [E], ops.expert_bias) is added to the fp16 scores before they are ranked (AddExperts,
+        add_skilled_experts.py:55; score_out then holds the biased scores), k (optional) replaces self.k for this call
+        (its int(0.8 * k), :57). With both None the launches are exactly those of a call without them.
 
         When the caller (FeedForward) allows it and the experts are balanced, the fused path runs instead:
         the projection GEMM's epilogue computes value*act(gate) and the expert scores, a small kernel applies
@@ -220,13 +223,15 @@ class GEGLU(nn.Module):
                 score = score_out if score_out is not None else \
                     torch.empty((x2.shape[0], routing.E), dtype=torch.float16, device=x.device)
                 out = ops.linear_geglu(x2, w_il, b_il, act, score=score, esize=routing.esize, ln=lnf)
+                if bias is not None:
+                    ops.score_bias(score, bias)  # in place, between the epilogue's scores and the top-k that ranks them
                 if FUSED_KEEP and routing.F % 64 == 0:
                     # the dropped experts' neurons are zeroed by the down projection as it reads them
                     # (sdmoe_linear_keep); `out` is then the unmasked product, an operand only FeedForward consumes
-                    keep = ops.moe_topk_keep(score, routing, x2.shape[0], removed=removed, sel_out=sel_out)
+                    keep = ops.moe_topk_keep(score, routing, x2.shape[0], removed=removed, sel_out=sel_out, k=k)
                     self._out_keep = (keep, out.data_ptr())
                 else:
-                    ops.moe_topk_mask(out, score, routing, removed=removed, sel_out=sel_out)
+                    ops.moe_topk_mask(out, score, routing, removed=removed, sel_out=sel_out, k=k)
                 self._out_perm = (routing, out.data_ptr())
             return out.view(*shp[:-1], self.inner_dim), None
         if norm is not None:
@@ -234,7 +239,7 @@ class GEGLU(nn.Module):
         y = self.proj.run(x2)
         gate = torch.empty((x2.shape[0], self.inner_dim), dtype=torch.float16, device=x.device) if want_gate else None
         out = ops.geglu_route(y, self.routing(), act_code(self.gelu), removed=removed, gate_out=gate, sel_out=sel_out,
-                              score_out=score_out)
+                              score_out=score_out, k=k, bias=bias)
         out = out.view(*shp[:-1], self.inner_dim)
         return out, (gate.view(*shp[:-1], self.inner_dim) if want_gate else None)
 

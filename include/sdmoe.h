@@ -185,6 +185,32 @@ int sdmoe_geglu_route(const void* Y, long ldy, int M, int F, int E, int k, int a
                       void* gate_out, long ldg, unsigned* sel_out, void* score_out, void* stream);
 
 /*
+ * Per-expert score bias: AddExperts.hook_fn (neuron_receivers/add_skilled_experts.py:35-71), the counterpart of
+ * RemoveExperts that pushes a concept's experts INTO every token's top-k. Its one line over MOEFy.hook_fn,
+ *   score[:, expert_indx] = score[:, expert_indx] + 5.0 * std[expert_indx]          (:55)
+ * is one more rounding point on the fp16 score, between the kernel that produces it and the kernel that ranks it;
+ * the reference's k' = int(0.8 * k) (:57) is the run-time k of the existing top-k entry points.
+ *   bias [E] fp16: fp16(5.0 * fp16(std[e])) at the listed experts, +0 elsewhere (the host forms it with the
+ *   reference's own torch operations: first rounding point). A listed duplicate is applied once.
+ *
+ *  sdmoe_score_bias: out[m, e] = fp16(score[m, e] + bias[e]) for m < M, e < E (second rounding point: the fp16 + fp16
+ *    sum is exact in fp32, so one round-to-nearest-even conversion is the reference's fp16 add). score / out [M, E]
+ *    fp16 with row strides ld_score / ld_out >= E; columns >= E of a strided row are neither read nor written.
+ *    out == score (in place) is allowed; any other overlap is not. 1 <= E <= 256, any M. 16-byte loads and stores
+ *    when E, both strides are multiples of 8 and all three pointers 16-byte aligned, else 2-byte ones. Feeds
+ *    sdmoe_moe_topk_keep / sdmoe_moe_topk_mask (fused path: sdmoe_linear_geglu -> sdmoe_score_bias -> top-k at k').
+ *  sdmoe_geglu_route_bias: sdmoe_geglu_route with that add inside the kernel (unfused path): after the
+ *    removed-expert zeroing, score[e] = fp16(score[e] + bias[e]) before score_out is written and before the top-k
+ *    ranks it. bias == NULL: bit-identical to sdmoe_geglu_route (which is this entry point with bias NULL).
+ */
+int sdmoe_score_bias(const void* score, long ld_score, int M, int E, const void* bias, void* out, long ld_out,
+                     void* stream);
+int sdmoe_geglu_route_bias(const void* Y, long ldy, int M, int F, int E, int k, int act, const int* labels,
+                           const int* e_off, const int* e_nid, const unsigned* removed_bits, void* out, long ldo,
+                           void* gate_out, long ldg, unsigned* sel_out, void* score_out, const void* bias,
+                           void* stream);
+
+/*
  * Fused form of the same routing for balanced experts (the reference's KMeansConstrained split: every expert
  * has esize neurons, esize | 40), in two launches and without the [M, 2F] projection output:
  *  1. sdmoe_linear_geglu: P[m, n] = fp16(fp16(x W_v^T + b_v) * fp16(act(fp16(x W_g^T + b_g)))) for all F neurons
