@@ -56,6 +56,9 @@ struct TileRule { int tile, ks_want, stages_want; };
 // the gemm_kernel instantiations the library is built with: launch() reaches exactly these
 constexpr bool built(int mode, int tile) {
   if (mode_halo(mode)) return (tile == T128x320 && mode != MODE_CONVHUP64) || (tile == T256x320 && mode != MODE_CONVHUP16);
+  if (mode == MODE_CONV_UP2X)  // the tiles choose_tile's dense rules and the tile knob's values 1-4 and 6 reach
+    return tile == T128x160 || tile == T64x160 || tile == T256x320 || tile == T256x160_42 || tile == T128x320 ||
+           tile == T128x64 || tile == T128x128 || tile == T64x128;
   if (mode_geglu(mode))  // BN in {160, 320} only (wave tile width 80 = 40 neurons = whole experts)
     return tile == T128x160 || tile == T64x160 || tile == T256x320 || tile == T256x160_42 || tile == T256x320_42 ||
            (tile == T128x160_42 && mode != MODE_GEGLU_GT);  // (no room for the GELU table behind that tile's staging)
@@ -125,7 +128,7 @@ Plan tile_plan(int mode, int tile, const GemmParams& p, int ksplit, int stages_w
   // M-fastest order for split-K convs only: their weight slices (up to 29 MB at the 16x16 level) were re-fetched by
   // every XCD (PMC FETCH_SIZE of the split-K conv launches 140 -> 46 MB, time neutral); the M = 1024 split-K linears
   // measured 2 us slower with it
-  pl.mfast = (pl.ksplit > 1 && knob(KNOB_MFAST) && (mode == MODE_CONV || mode == MODE_CONV_UP)) ? 1 : 0;
+  pl.mfast = (pl.ksplit > 1 && knob(KNOB_MFAST) && (mode == MODE_CONV || mode == MODE_CONV_UP || mode == MODE_CONV_UP2X)) ? 1 : 0;
   // 64-deep K-steps (a 32-deep 4/5-stage ring measured slower on every shape; the kernel is generic in BK).
   // 4-wave tiles: 2-stage ring (2 workgroups/CU) when the grid has >= ~300 workgroups, else 3-stage; 8-wave
   // tiles: 3-stage where it fits in LDS -- measured crossovers on MI355X.
@@ -316,6 +319,8 @@ TileRule choose_tile(int mode, const GemmParams& p) {
   }
   // (the keep-masked down projection at one prompt, <= 128 tiles of 128x160, runs on 64x160 tiles through the plain
   // rule below: 22.3 vs 29.5 us at the 64x64 level, profiles/r05_b1_geglu_keep_tiles.txt)
+  // (the collapsed upsample convs under 180 tiles of 256x320 take this rule too: 128x320 tiles ran 62.5 vs 68.0 us in a
+  // warm loop but 66.9 vs 62.9 us in the pipeline's kernel trace, 8 -> 16 at 16 images, profiles/upconv_collapse_ab.txt)
   if (p.N % 160 == 0 && p.K >= 2560 && nt160_128 < 300 && !(mode == MODE_CONV && p.stride == 2))
     return {T256x160_42, 0, 0};
   if (mode == MODE_CONV_UP) return {p.N % 160 == 0 ? T128x160 : T128x128, 0, 0};
@@ -386,7 +391,7 @@ int launch_kernel(const Plan& pl, const GemmParams& p, dim3 grid, hipStream_t s)
 }
 
 // launch_kernel<MODE, tile> at MODE * NTILE + tile
-constexpr int NMODE = MODE_GEGLU_GT + 1;
+constexpr int NMODE = MODE_CONV_UP2X + 1;
 using LaunchFn = int (*)(const Plan&, const GemmParams&, dim3, hipStream_t);
 template <int... KEY>
 constexpr std::array<LaunchFn, sizeof...(KEY)> launch_table(std::integer_sequence<int, KEY...>) {
@@ -415,7 +420,8 @@ int launch(const Plan& pl, GemmParams p, float* ws, hipStream_t s) {
     long nchunk = (long)p.M * (p.N / 8);
     int g = (int)((nchunk + 255) / 256);
     if (g > 2048) g = 2048;
-    splitk_reduce_kernel<<<g, 256, 0, s>>>(p);
+    if (pl.mode == MODE_CONV_UP2X) splitk_reduce_up2x_kernel<<<g, 256, 0, s>>>(p);
+    else splitk_reduce_kernel<<<g, 256, 0, s>>>(p);
     SDMOE_CHECK_LAUNCH();
   }
   return SDMOE_OK;
@@ -876,6 +882,51 @@ extern "C" int sdmoe_conv3x3(const void* X, long ldx, int nimg, int H, int W, in
   conv_shape(p, nimg, H, W, Cin, 0, Cout, stride, upsample, act);
   if (const int st = fill_conv(p, X, ldx, Wt, bias, coladd, coladd_bstride, R, ldr, nullptr, 0, Y, ldy)) return st;
   return launch(plan_conv(p, workspace, workspace_floats), p, workspace, (hipStream_t)stream);
+}
+
+// the implicit GEMM of the phase-collapsed nearest-2x upsample conv (MODE_CONV_UP2X): rows = low-res pixels, columns =
+// (phase, output channel), K = (64-channel slice, 2x2 tap, channel)
+namespace {
+
+void up2x_shape(GemmParams& p, int nimg, int H, int W, int Cin, int Cout) {
+  p.M = nimg * H * W; p.N = 4 * Cout; p.K = 4 * Cin; p.act = ACT_NONE;
+  p.ldw = 4L * Cin; p.rows_per_batch = H * W;
+  p.H = H; p.Wd = W; p.Cin = Cin; p.OH = H; p.OW = W; p.stride = 1; p.upsample = 0;
+}
+
+// the plan of sdmoe_conv_up2x: the dense tile rules on the collapsed GEMM; false where the chosen tile's columns would
+// straddle two phases (Cout % BN != 0) or the tile is not built for the mode
+bool plan_up2x(const GemmParams& p, int Cout, bool ws, long ws_floats, Plan* pl) {
+  *pl = plan_launch(MODE_CONV_UP2X, p, ws, ws_floats);
+  return built(MODE_CONV_UP2X, pl->tile) && Cout % kTile[pl->tile].bn == 0;
+}
+
+}  // namespace
+
+extern "C" int sdmoe_conv_up2x(const void* X, long ldx, int nimg, int H, int W, int Cin, const void* Wc, const void* bias,
+                               void* Y, long ldy, int Cout, float* workspace, long workspace_floats, void* stream) {
+  if (nimg == 0) return SDMOE_OK;
+  if (!X || !Wc || !Y || nimg < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return SDMOE_EARG;
+  if (Cin % 64 || Cout % 8 || ldx % 8 || ldy % 8) return SDMOE_ESHAPE;
+  if (4L * nimg * H * W >= (long)OOB) return SDMOE_ESHAPE;
+  GemmParams p{};
+  up2x_shape(p, nimg, H, W, Cin, Cout);
+  Plan pl;
+  if (!plan_up2x(p, Cout, workspace, workspace_floats, &pl)) return SDMOE_EUNSUP;
+  if (const int st = fill_conv(p, X, ldx, Wc, bias, nullptr, 0, nullptr, 0, nullptr, 0, Y, ldy)) return st;
+  return launch(pl, p, workspace, (hipStream_t)stream);
+}
+
+extern "C" int sdmoe_conv_up2x_plan(int nimg, int H, int W, int Cin, int Cout, long workspace_floats, int* out) {
+  if (!out || nimg <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || workspace_floats < 0) return SDMOE_EARG;
+  if (Cin % 64 || Cout % 8) return SDMOE_ESHAPE;
+  GemmParams p{};
+  up2x_shape(p, nimg, H, W, Cin, Cout);
+  Plan pl;
+  if (!plan_up2x(p, Cout, workspace_floats > 0, workspace_floats, &pl)) return SDMOE_EUNSUP;
+  const TileShape& t = kTile[pl.tile];
+  out[0] = t.bm; out[1] = t.bn; out[2] = t.wmw; out[3] = t.wnw; out[4] = pl.stages; out[5] = pl.ksplit; out[6] = pl.kchunk;
+  return SDMOE_OK;
 }
 
 extern "C" int sdmoe_conv3x3_sc(const void* X, long ldx, int nimg, int H, int W, int Cin, const void* Wt,

@@ -145,7 +145,11 @@ SDMOE_DEV void epilogue8(const GemmParams& p, int m, int n, float (&v)[8]) {
 // GEMM_LN / GEGLU_LN: GEMM / GEGLU with the LayerNorm of the A rows folded in (row statistics from the A tiles)
 enum { MODE_GEMM = 0, MODE_CONV = 1, MODE_CONV_UP = 2, MODE_GEGLU = 3, MODE_KEEP = 4, MODE_WMASK = 5, MODE_KEEPW = 6,
        MODE_GEMM_LN = 7, MODE_GEGLU_LN = 8, MODE_CONVH64 = 9, MODE_CONVH32 = 10, MODE_CONVH16 = 11,
-       MODE_CONVHUP64 = 12, MODE_CONVHUP32 = 13, MODE_CONVHUP16 = 14, MODE_GEGLU_GT = 15 };
+       MODE_CONVHUP64 = 12, MODE_CONVHUP32 = 13, MODE_CONVHUP16 = 14, MODE_GEGLU_GT = 15, MODE_CONV_UP2X = 16 };
+// MODE_CONV_UP2X: the nearest-2x upsample conv collapsed to four 2x2 phase convs on the LOW-resolution image
+// (sdmoe_conv_up2x): M = low-res pixels, N = 4 Cout (phase 2 py + px major), K = 4 Cin (64-channel slice, tap 2 a + c,
+// channel). A tile's columns lie in one phase (Cout % BN == 0); tap (a, c) of output pixel (r, q) reads input pixel
+// (r + py + a - 1, q + px + c - 1), zero outside; the epilogue stores row (b, r, q) to output row up2x_out_row()
 // MODE_GEGLU_GT: the routed GEGLU with act = GELU from the registered table (its own instantiation: a third epilogue
 // variant inside MODE_GEGLU pushed the 256x320 kernel past 256 VGPRs into scratch, 115 -> 494 us)
 // halo-tiled stride-1 3x3 conv (MODE_CONVH<W>, image width W): a tile is BM / W whole output rows of one image; per
@@ -154,6 +158,14 @@ enum { MODE_GEMM = 0, MODE_CONV = 1, MODE_CONV_UP = 2, MODE_GEGLU = 3, MODE_KEEP
 // MODE_CONVHUP<OW>: the same for the fused nearest-2x upsample conv (output width OW): the halo is the
 // (BM / OW / 2 + 2) x (OW / 2 + 2) LOW-resolution input patch; output pixel (oh, ow) at tap (kh, kw) reads input
 // ((oh + kh - 1) >> 1, (ow + kw - 1) >> 1) -- two lanes of a fragment share each input row (an LDS broadcast)
+// MODE_CONV_UP2X row map, shared by the fp16 epilogue and splitk_reduce_up2x_kernel: GEMM row m = low-res pixel (b, r, q)
+// of nimg H x W images, phase ph = 2 py + px -> row of the 2H x 2W output image
+SDMOE_DEV long up2x_out_row(int m, int H, int W, int ph) {
+  const int hw = H * W;
+  const int b = m / hw, rq = m - b * hw;
+  const int r = rq / W, q = rq - r * W;
+  return ((long)(b * 2 * H + 2 * r + (ph >> 1)) * (2 * W) + 2 * q + (ph & 1));
+}
 constexpr bool mode_halo(int mode) { return mode >= MODE_CONVH64 && mode <= MODE_CONVHUP16; }
 constexpr bool mode_halo_up(int mode) { return mode >= MODE_CONVHUP64 && mode <= MODE_CONVHUP16; }
 constexpr int halo_w(int mode) {  // OUTPUT width
@@ -235,7 +247,8 @@ template <int BM_, int BN_, int WMW_, int WNW_, int MODE_, int NSTAGE_, int BKT_
 struct GemmCfg {
   // BK: K per stage, 64 (128-B rows) or 32 (64-B rows, deeper ring)
   static constexpr int BM = BM_, BN = BN_, WMW = WMW_, WNW = WNW_, MODE = MODE_, NSTAGE = NSTAGE_, BK = BKT_;
-  static constexpr bool CONV = MODE == MODE_CONV || MODE == MODE_CONV_UP, GEGLU = mode_geglu(MODE), LN = mode_ln(MODE);
+  static constexpr bool UP2X = MODE == MODE_CONV_UP2X;
+  static constexpr bool CONV = MODE == MODE_CONV || MODE == MODE_CONV_UP || UP2X, GEGLU = mode_geglu(MODE), LN = mode_ln(MODE);
   static constexpr bool AKEEP = mode_akeep(MODE), WKEEP = mode_wmask(MODE), KEEP = AKEEP || WKEEP;
   static constexpr bool HALO = mode_halo(MODE), HUP = mode_halo_up(MODE);
   static constexpr GemmLayout lay() { return GemmLayout{BM, BN, WMW, WNW, MODE, NSTAGE, BK}; }
@@ -325,6 +338,8 @@ __global__ __launch_bounds__(64 * WMW * WNW, (NSTAGE == 2 && (WMW * WNW == 4 || 
   const int ks0 = split * p.kchunk;
   const int ks1 = min(nk_total, ks0 + p.kchunk);
   const int nk = ks1 - ks0;
+  // MODE_CONV_UP2X: the phase this tile's columns lie in (Cout % BN == 0, host check) and its row / column shift
+  const int up_ph = G::UP2X ? n0 / (p.N >> 2) : 0, up_py = up_ph >> 1, up_px = up_ph & 1;
 
   // ---- LDS-DMA sources: buffer loads through two SRDs (A, W); an out-of-range offset (OOB) is dropped by the
   // hardware range check and lands as zeros, which gives conv halo rows and M/N tails for free.
@@ -360,6 +375,15 @@ __global__ __launch_bounds__(64 * WMW * WNW, (NSTAGE == 2 && (WMW * WNW == 4 || 
 #pragma unroll
           for (int t = 0; t < 9; ++t) {
             const int y = ih + t / 3 - 1, x = iw + t % 3 - 1;
+            msk |= (y >= 0 && y < p.H && x >= 0 && x < p.Wd) ? (1u << t) : 0u;
+          }
+          amask[j] = msk;
+        } else if (G::UP2X) {  // tap-(1 - py, 1 - px) pixel = the low-res pixel itself; bit t = 2 a + c in bounds
+          avoff[j] = (unsigned)(((long)(b * p.H + oh) * p.Wd + ow) * p.lda * 2) + chb;
+          unsigned msk = 0;
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const int y = oh + up_py + (t >> 1) - 1, x = ow + up_px + (t & 1) - 1;
             msk |= (y >= 0 && y < p.H && x >= 0 && x < p.Wd) ? (1u << t) : 0u;
           }
           amask[j] = msk;
@@ -425,7 +449,8 @@ __global__ __launch_bounds__(64 * WMW * WNW, (NSTAGE == 2 && (WMW * WNW == 4 || 
   const int csl = G::CONV ? p.Cin / BK : 0;
   const __amdgpu_buffer_rsrc_t rsA2 =
       __builtin_amdgcn_make_buffer_rsrc((void*)p.A2, (short)0, p.A2 ? p.a2_bytes : 0, 0x00020000);
-  int st_c = G::CONV ? ks0 / 9 : 0, st_tap = G::CONV ? ks0 - st_c * 9 : 0;
+  constexpr int NTAP = G::UP2X ? 4 : 9;  // K-steps per 64-channel slice
+  int st_c = G::CONV ? ks0 / NTAP : 0, st_tap = G::CONV ? ks0 - st_c * NTAP : 0;
   if (MODE == MODE_CONV && ks0 >= 9 * csl) { st_c = csl + (ks0 - 9 * csl); st_tap = 0; }
 
   auto issue_stage = [&](int ks, int buf) {
@@ -440,6 +465,17 @@ __global__ __launch_bounds__(64 * WMW * WNW, (NSTAGE == 2 && (WMW * WNW == 4 || 
       ++st_c;
 #pragma unroll
       for (int j = 0; j < L.A_PW; ++j) bld16(rsA2, sa + a_dst(j), avoff2[j] == OOB ? OOB : avoff2[j] + c2b, 0);
+    } else if constexpr (G::UP2X) {  // tap (a, c) of the tile's phase: input pixel shifted by (py + a - 1, px + c - 1)
+      const int tap = st_tap;
+      const int c0b = st_c * BK * 2;
+      if (++st_tap == 4) { st_tap = 0; ++st_c; }
+      const unsigned tapoff =
+          (unsigned)(((up_py + (tap >> 1) - 1) * p.Wd + (up_px + (tap & 1) - 1)) * (int)p.lda * 2 + c0b);
+#pragma unroll
+      for (int j = 0; j < L.A_PW; ++j) {
+        const unsigned vo = ((amask[j] >> tap) & 1u) ? avoff[j] + tapoff : OOB;
+        bld16(rsA, sa + a_dst(j), vo, 0);
+      }
     } else {
       const int tap = st_tap;
       const int kh = tap >= 6 ? 2 : (tap >= 3 ? 1 : 0);
@@ -1026,10 +1062,16 @@ __global__ __launch_bounds__(64 * WMW * WNW, (NSTAGE == 2 && (WMW * WNW == 4 || 
     // rows: 29 -> 33 us for linear+res at 64x64) and the GEGLU epilogue on fp16 staging (170 -> 179 us); an
     // activation's code keeps the unrolled fragment loop from unrolling (acc then lives in scratch).
     half4 b4[L.FN];
+    // MODE_CONV_UP2X: GEMM column n = phase * Cout + channel -> bias and output column n - ncol0, output row by the map
+    const int ncol0 = G::UP2X ? up_ph * (p.N >> 2) : 0;
+    auto c_at = [&](int m, int n) -> half_t* {
+      if constexpr (G::UP2X) return p.C + up2x_out_row(m, p.H, p.Wd, up_ph) * p.ldc + (n - ncol0);
+      else return p.C + (long)m * p.ldc + n;
+    };
 #pragma unroll
     for (int j = 0; j < L.FN; ++j) {
       const int n = nw + 16 * j + 4 * fg;
-      b4[j] = (!G::LN && p.bias && n < p.N) ? *reinterpret_cast<const half4*>(p.bias + n) : (half4){0, 0, 0, 0};
+      b4[j] = (!G::LN && p.bias && n < p.N) ? *reinterpret_cast<const half4*>(p.bias + (n - ncol0)) : (half4){0, 0, 0, 0};
     }
     if (!G::WKEEP && p.epi_direct) {  // (the Wanda-masked tiles: no registers to spare for it)
       // Direct fp16 stores, no LDS staging (sdmoe_tune knob 23): per fragment row and pair of fragments (j, j + 1)
@@ -1091,7 +1133,7 @@ __global__ __launch_bounds__(64 * WMW * WNW, (NSTAGE == 2 && (WMW * WNW == 4 || 
               for (int r = 0; r < 8; ++r) o[r] = (half_t)((float)o[r] + (float)rr[r]);
             }
             if (p.diag & 8) asm volatile("" ::"v"(o));
-            else *reinterpret_cast<half8*>(p.C + (long)m * p.ldc + n) = o;
+            else *reinterpret_cast<half8*>(c_at(m, n)) = o;
           }
         }
         if constexpr (L.FN % 2) {
@@ -1104,7 +1146,7 @@ __global__ __launch_bounds__(64 * WMW * WNW, (NSTAGE == 2 && (WMW * WNW == 4 || 
               for (int r = 0; r < 4; ++r) o[r] = (half_t)((float)o[r] + (float)rr[r]);
             }
             if (p.diag & 8) asm volatile("" ::"v"(o));
-            else *reinterpret_cast<half4*>(p.C + (long)m * p.ldc + n) = o;
+            else *reinterpret_cast<half4*>(c_at(m, n)) = o;
           }
         }
       }
@@ -1185,12 +1227,13 @@ __global__ __launch_bounds__(64 * WMW * WNW, (NSTAGE == 2 && (WMW * WNW == 4 || 
           for (int j = 0; j < 8; ++j) o[j] = (half_t)((float)o[j] + (float)rr[it][j]);
         }
         if (p.diag & 8) asm volatile("" ::"v"(o));
-        else *reinterpret_cast<half8*>(p.C + (long)m * p.ldc + n) = o;
+        else *reinterpret_cast<half8*>(c_at(m, n)) = o;
       }
       wave_sync();
     }
     return;
   }
+  if constexpr (G::UP2X) return;  // (sdmoe_conv_up2x has no activation and no residual: the fp16 path above)
   if constexpr (G::GEGLU) {
     // lane-derived epilogue values from an opaque copy of the lane id: nothing of this epilogue can be hoisted
     // above the main loop (hoisted addresses kept the table-GELU variant's K loop in scratch)
@@ -1348,6 +1391,34 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmParams p) {
       v[4] += b[0]; v[5] += b[1]; v[6] += b[2]; v[7] += b[3];
     }
     epilogue8(p, m, n, v);
+  }
+}
+
+// the same combine for MODE_CONV_UP2X: slab column n = phase * Cout + channel (Cout % 8 == 0: a chunk lies in one
+// phase), + bias[channel], stored at the phase's output row (up2x_out_row, as the fp16 epilogue)
+__global__ __launch_bounds__(256) void splitk_reduce_up2x_kernel(GemmParams p) {
+  const long nchunk = (long)p.M * (p.N / 8);
+  const int cout = p.N >> 2;
+  for (long id = blockIdx.x * 256L + threadIdx.x; id < nchunk; id += (long)gridDim.x * 256) {
+    const int m = (int)(id / (p.N / 8)), n = (int)(id % (p.N / 8)) * 8;
+    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int s = 0; s < p.ksplit; ++s) {
+      const float* sp = p.part + ((long)s * p.M + m) * p.N + n;
+      float4v a = *reinterpret_cast<const float4v*>(sp), b = *reinterpret_cast<const float4v*>(sp + 4);
+      v[0] += a[0]; v[1] += a[1]; v[2] += a[2]; v[3] += a[3];
+      v[4] += b[0]; v[5] += b[1]; v[6] += b[2]; v[7] += b[3];
+    }
+    const int ph = n / cout, c = n - ph * cout;
+    if (p.bias) {
+      const half8 bb = *reinterpret_cast<const half8*>(p.bias + c);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] += (float)bb[j];
+    }
+    half8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (half_t)v[j];
+    if (p.diag & 8) asm volatile("" ::"v"(o));
+    else *reinterpret_cast<half8*>(p.C + up2x_out_row(m, p.H, p.Wd, ph) * p.ldc + c) = o;
   }
 }
 

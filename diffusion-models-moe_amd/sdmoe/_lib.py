@@ -25,6 +25,9 @@ SIGNATURES = {
     "sdmoe_conv3x3_sc": [_P, _L, _I, _I, _I, _I, _P, _P, _P, _L, _P, _L, _I, _P, _L, _I, _I, _P, _L, _P],
     "sdmoe_conv3x3_gn": [_P, _L, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _L, _P, _L, _P, _L, _I, _P, _L, _I, _P, _L,
                          _P],
+    # (callers probe sdmoe_conv_up2x with has(): an SDMOE_AB=1 library from before it takes sdmoe_conv3x3's upsample path)
+    "sdmoe_conv_up2x": [_P, _L, _I, _I, _I, _I, _P, _P, _P, _L, _I, _P, _L, _P],
+    "sdmoe_conv_up2x_plan": [_I, _I, _I, _I, _I, _L, _P],
     "sdmoe_groupnorm_apply": [_P, _L, _I, _I, _I, _P, _P, _I, _P, _L, _P],
     "sdmoe_mask_weight": [_P, _P, _L, _L, _P, _P],
     "sdmoe_groupnorm_stats": [_P, _L, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _L, _P],

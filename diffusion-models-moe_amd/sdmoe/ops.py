@@ -463,6 +463,92 @@ def conv3x3_launch(xp, ldx, nimg, H, W, Cin, w, bias, coladd, coladd_bstride, rp
     return out
 
 
+# Nearest-2x upsample + 3x3 conv as four 2x2 convs on the low-resolution image (sdmoe_conv_up2x):
+# [phase row or column p][2x2 row or column a] -> the 3x3 taps that land on that input pixel
+_UP2X_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+def up2x_collapse(w):
+    """[Cout, 3, 3, Cin] -> [4, Cout, 2, 2, Cin] in w's dtype: phase 2 py + px of a nearest-2x upsampled image reads
+    a 2x2 input neighbourhood, and the taps that land on one input pixel are summed (_UP2X_TAPS, rows and columns
+    alike). Exact in exact arithmetic: output pixel (2r + py, 2q + px) = sum over (a, c) of
+    result[2 py + px, :, a, c] . x[r + py + a - 1, q + px + c - 1]."""
+    Cout, kh, kw, Cin = w.shape
+    if (kh, kw) != (3, 3):
+        raise ValueError(f"up2x_collapse: expected [Cout, 3, 3, Cin], got {tuple(w.shape)}")
+    out = w.new_empty((4, Cout, 2, 2, Cin))
+    for py in range(2):
+        for px in range(2):
+            for a in range(2):
+                for c in range(2):
+                    taps = [w[:, i, j] for i in _UP2X_TAPS[py][a] for j in _UP2X_TAPS[px][c]]
+                    out[2 * py + px, :, a, c] = sum(taps[1:], taps[0])
+    return out
+
+
+def conv_up2x_weight(w):
+    """The operand of conv_up2x from a [Cout, 3, 3, Cin] filter (taps-last, as conv_weight takes): fp16
+    [4, Cout, Cin/64, 2, 2, 64] -- phase, then conv_weight's K order (64-channel slice, tap, channel). Summed in fp32,
+    rounded to fp16 once. Made once per weight version (16/9 of the filter's bytes), not per call."""
+    Cout, _, _, Cin = w.shape
+    if Cin % 64:
+        raise ValueError(f"conv_up2x_weight: Cin % 64 != 0 in {tuple(w.shape)}")
+    wc = up2x_collapse(w.float()).half()
+    return wc.reshape(4, Cout, 4, Cin // 64, 64).permute(0, 1, 3, 2, 4).reshape(4, Cout, Cin // 64, 2, 2, 64).contiguous()
+
+
+def conv_up2x_plan(nimg, H, W, Cin, Cout, workspace_floats=WS_FLOATS):
+    """The launch sdmoe_conv_up2x would make for nimg H x W x Cin images: {"tile", "waves", "stages", "ksplit",
+    "kchunk"}, or None where it refuses the shape (or the loaded library is an SDMOE_AB=1 build without it)."""
+    lib = _lib.load()
+    if not _lib.has(lib, "sdmoe_conv_up2x_plan"):
+        return None
+    out = (ctypes.c_int * 7)()
+    st = lib.sdmoe_conv_up2x_plan(nimg, H, W, Cin, Cout, workspace_floats, out)
+    if st in (-2, -3):
+        return None
+    _lib.check(st, "sdmoe_conv_up2x_plan")
+    return {"tile": (out[0], out[1]), "waves": (out[2], out[3]), "stages": out[4], "ksplit": out[5], "kchunk": out[6]}
+
+
+def conv_up2x(x, nimg, H, W, wc, bias=None, out=None, *, fallback=None):
+    """conv3x3(nearest-2x upsample of x) on NHWC x viewed as [nimg*H*W, Cin] -> [nimg*2H*2W, Cout], from the
+    phase-collapsed weight wc (conv_up2x_weight). Where the kernel refuses the shape (-3: Cout no multiple of the
+    chosen tile's columns) the conv runs as conv3x3(..., upsample=True) on `fallback`, the filter in conv_weight's
+    layout; without one that is an error."""
+    xp, ldx = _rows(x, "x")
+    Cin = x.shape[1]
+    if wc.dim() != 6 or wc.shape[0] != 4 or tuple(wc.shape[2:]) != (Cin // 64, 2, 2, 64) or Cin % 64:
+        raise ValueError(f"conv_up2x: weight {tuple(wc.shape)} is not the [4, Cout, Cin/64, 2, 2, 64] layout for "
+                         f"Cin={Cin} (ops.conv_up2x_weight)")
+    Cout = wc.shape[1]
+    if x.shape[0] != nimg * H * W:
+        raise ValueError("conv_up2x: rows != nimg*H*W")
+    if out is None:
+        out = torch.empty((nimg * 4 * H * W, Cout), dtype=torch.float16, device=x.device)
+    elif out.shape[0] != nimg * 4 * H * W or out.shape[1] != Cout:
+        raise ValueError(f"conv_up2x: out {tuple(out.shape)} is not [{nimg * 4 * H * W}, {Cout}]")
+    op, ldy = _rows(out, "out")
+    if conv_up2x_launch(xp, ldx, nimg, H, W, Cin, wc, bias, out, op, ldy, Cout) is not None:
+        return out
+    if fallback is None:
+        raise _lib.SdmoeError(f"sdmoe_conv_up2x refuses Cout={Cout} at {nimg} x {H} x {W} and no fallback filter was given")
+    return conv3x3(x, nimg, H, W, fallback, bias, upsample=True, out=out)
+
+
+def conv_up2x_launch(xp, ldx, nimg, H, W, Cin, wc, bias, out, op, ldy, Cout):
+    """The sdmoe_conv_up2x launch alone; None when the kernel refuses the shape (-3). Not a conv3x3_launch: that
+    function's callers count 9-tap FLOPs per launch, and this kernel executes 4/9 of them."""
+    lib = _lib.load()
+    ws = _workspace(out.device)
+    st = lib.sdmoe_conv_up2x(xp, ldx, nimg, H, W, Cin, _dev(wc, "wc"), _ptr(bias), op, ldy, Cout, ws.data_ptr(),
+                             ws.numel(), _stream())
+    if st == -3:
+        return None
+    _lib.check(st, "sdmoe_conv_up2x")
+    return out
+
+
 def groupnorm_stats(x, nimg, HW, gamma, beta, eps, groups=32):
     """Per-(image, channel) fp32 (scale, shift) of GroupNorm(groups) over x viewed as [nimg*HW, C]."""
     lib = _lib.load()

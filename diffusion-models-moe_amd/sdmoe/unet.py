@@ -38,6 +38,9 @@ FUSED_SC = os.environ.get("SDMOE_FUSED_SC", "1") != "0"
 # latents of >= 32x32 (SDMOE_FUSED_GN=0: GroupNorm apply pass + proj_in, A/B)
 FUSED_GN = os.environ.get("SDMOE_FUSED_GN", "1") != "0"
 GN_FOLD_MIN_HW = 1024
+# Upsample2D's nearest-2x + 3x3 conv as four 2x2 phase convs on the low-resolution image, 4/9 of the MFMA work
+# (sdmoe_conv_up2x; SDMOE_UPCONV_COLLAPSE=0: the fused-upsample conv of sdmoe_conv3x3, A/B)
+UPCONV_COLLAPSE = os.environ.get("SDMOE_UPCONV_COLLAPSE", "1") != "0"
 IN_PAD = 64    # conv_in input channels padded 4 -> 64 (K-step of the implicit GEMM)
 OUT_PAD = 8    # conv_out output channels padded 4 -> 8 (16-B epilogue stores)
 
@@ -581,6 +584,28 @@ class Sampler(nn.Module):
     def __init__(self, conv):
         super().__init__()
         self.conv = conv
+        self._up2x_key = None
+        self._up2x_w = None
+
+    def _collapsed_weight(self):
+        """conv's filter collapsed to the four 2x2 phase filters (ops.conv_up2x_weight), made once per weight version
+        (keyed as FeedForward._down_weight_permuted: an in-place edit recomputes it). 16/9 of the filter's bytes."""
+        w = self.conv.weight
+        key = (w.data_ptr(), w._version)
+        if self._up2x_key != key:
+            Cout, nsl = w.shape[0], w.shape[1]
+            taps_last = w.data.permute(0, 2, 3, 1, 4).reshape(Cout, 3, 3, nsl * 64)  # conv_weight's layout undone
+            self._up2x_w = ops.conv_up2x_weight(taps_last)
+            self._up2x_key = key
+        return self._up2x_w
+
+    def upsample(self, x, nimg, H, W, out):
+        """out = conv(nearest-2x upsample of x): the phase-collapsed kernel where it takes the shape, else (or with
+        UPCONV_COLLAPSE off) the fused-upsample conv."""
+        c = self.conv
+        if UPCONV_COLLAPSE and ops.conv_up2x_plan(nimg, H, W, x.shape[1], c.weight.shape[0]) is not None:
+            return ops.conv_up2x(x, nimg, H, W, self._collapsed_weight(), c.bias, out=out, fallback=c.weight)
+        return ops.conv3x3(x, nimg, H, W, c.weight, c.bias, upsample=True, out=out)
 
 
 class Block(nn.Module):
@@ -850,8 +875,7 @@ class UNet2DConditionModel(nn.Module):
                 if last_in_block:
                     if has_up:
                         nb, ncp, _ = up_in[idx]
-                        c = blk.upsamplers[0].conv
-                        ops.conv3x3(o, nimg, hh, hh, c.weight, c.bias, upsample=True, out=nb[:, :ncp])
+                        blk.upsamplers[0].upsample(o, nimg, hh, hh, nb[:, :ncp])
                     else:
                         final = o
 

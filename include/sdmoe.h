@@ -83,6 +83,26 @@ int sdmoe_conv3x3_gn(const void* X, long ldx, int nimg, int H, int W, int Cin, c
                      const float* gn_shift, int silu, const void* Wt, const void* bias, const void* coladd,
                      long coladd_bstride, const void* R, long ldr, const void* X2, long ldx2, int Cin2, void* Y,
                      long ldy, int Cout, float* workspace, long workspace_floats, void* stream);
+
+/*
+ * sdmoe_conv_up2x — the nearest-2x upsample + 3x3 conv (sdmoe_conv3x3 with upsample = 1, no coladd / activation /
+ * residual) collapsed to four 2x2 convs on the LOW-resolution image: output pixel (2r + py, 2q + px) reads only input
+ * pixels (r + py + a - 1, q + px + c - 1), a, c in {0, 1} (zero outside), so the taps that land on one input pixel
+ * have their weights summed ahead of time and the conv runs 4/9 of the MFMA work. X [nimg*H*W, Cin] (pixel stride
+ * ldx), Y [nimg*2H*2W, Cout] (row stride ldy), bias [Cout] or NULL.
+ * Wc [4][Cout][Cin/64][2][2][64] fp16: phase 2 py + px, then sdmoe_conv3x3's K order (64-channel slice, tap, channel);
+ * row a of phase row py sums kh {0} | {1, 2} (py = 0) or {0, 1} | {2} (py = 1), columns likewise (fp32 sums, rounded
+ * once: sdmoe/ops.py conv_up2x_weight). An implicit GEMM of M = nimg*H*W, N = 4 Cout, K = 4 Cin on the dense tile
+ * rules; every tile lies in one phase: -3 (unsupported) when Cout is no multiple of the chosen tile's columns -- the
+ * caller then runs sdmoe_conv3x3. Cin % 64 == 0, Cout % 8 == 0.
+ * Replaces: diffusers Upsample2D (F.interpolate(scale_factor=2.0, mode="nearest") + conv; external).
+ */
+int sdmoe_conv_up2x(const void* X, long ldx, int nimg, int H, int W, int Cin, const void* Wc, const void* bias, void* Y,
+                    long ldy, int Cout, float* workspace, long workspace_floats, void* stream);
+/* the launch sdmoe_conv_up2x would make: out[0..6] = tile rows, tile columns, waves along M, waves along N, ring
+ * stages, split-K factor, 64-deep K-steps per split; -3 where it refuses. Queries the CU count as sdmoe_gemm_plan. */
+int sdmoe_conv_up2x_plan(int nimg, int H, int W, int Cin, int Cout, long workspace_floats, int* out);
+
 /* Y = (SiLU?)(X * scale[img, c] + shift[img, c]) on [nimg*HW, C] (the GroupNorm apply; scale/shift from
  * sdmoe_groupnorm_stats). C % 8 == 0. */
 int sdmoe_groupnorm_apply(const void* X, long ldx, int nimg, int HW, int C, const float* scale, const float* shift,
