@@ -18,6 +18,13 @@ fc1 with quick_gelu/gelu in the epilogue -> fc2 with the residual add in its epi
 buffers, no in-place epilogues. A hooked CLIPMLP is deferred (skips its own forward) and the receiver's
 text_hook_fn computes it; the residual is then added by sdmoe_add.
 
+Vision tower and `CLIPModel` (end of this file): the image side of the reference's removal-quality scores
+(benchmarks/artist_removal.py:175-194), transformers' `vision_model.*` / `visual_projection` names. Its input is not
+a pixel_values tensor but the patch-embedding GEMM's A operand that `ops.clip_preprocess` writes (Pillow-exact
+resample, normalise, patchify: csrc/clip_image.hip), so the patch conv is one `sdmoe_linear`; `sdmoe_gather_rows`
+lays the class token and the position embeddings around the patch rows; the encoder layers are the text tower's,
+unmasked (`sdmoe_attention_short` up to 128 tokens, `sdmoe_attention` above). `sdmoe.scoring.ClipScorer` drives it.
+
 Tokenizer: the CLIP BPE vocabulary (vocab.json / merges.txt) is not available offline, so `SyntheticCLIPTokenizer`
 maps words to stable ids (crc32) with CLIP's BOS/EOS/padding and the 77-token truncation; any tokenizer with the
 transformers call signature (e.g. transformers.CLIPTokenizer on a local checkpoint directory) can replace it.
@@ -65,6 +72,13 @@ class CLIPTextConfig:
         """SDXL-base text_encoder_2 (OpenCLIP ViT-bigG text tower with projection; its tokenizer pads with '!')."""
         return CLIPTextConfig(hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, num_attention_heads=20,
                               hidden_act="gelu", projection_dim=1280, pad_token_id=0)
+
+    @staticmethod
+    def vit_b32():
+        """openai/clip-vit-base-patch32 text tower (the reference's scoring model): 512 wide, 8 heads, 512-d
+        projection."""
+        return CLIPTextConfig(hidden_size=512, intermediate_size=2048, num_hidden_layers=12, num_attention_heads=8,
+                              projection_dim=512)
 
     @staticmethod
     def tiny(width=64, layers=2, heads=2, act="quick_gelu", projection_dim=0):
@@ -170,12 +184,23 @@ class CLIPAttention(nn.Module):
             self._qkv_key = key
         return self._qkv
 
-    def run(self, h, nseq, L, residual, out):
+    def run(self, h, nseq, L, residual, out, causal=True):
         C = h.shape[1]
         w, b = self.fused_qkv()
         qkv = ops.linear(h, w, b)
-        a = ops.attention_short(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], nseq, L, self.num_heads, causal=True)
+        q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
+        if causal or L <= 128:
+            a = ops.attention_short(q, k, v, nseq, L, self.num_heads, causal=causal)
+        else:  # the vision tower's longer unmasked sequences (ViT-L/14: 257 tokens)
+            a = ops.attention(q, k, v, nseq, L, L, self.num_heads)
         return self.out_proj.run(a, residual=residual, out=out)
+
+
+class CLIPVisionAttention(CLIPAttention):
+    """CLIPAttention of the vision tower: no causal mask."""
+
+    def run(self, h, nseq, L, residual, out, causal=False):
+        return super().run(h, nseq, L, residual, out, causal=causal)
 
 
 class _LayerNorm(nn.Module):
@@ -437,3 +462,224 @@ def attach_text_encoders(pipe, seed: int = 0):
         pipe.tokenizer_2 = SyntheticCLIPTokenizer(pad_token_id=c2.pad_token_id)
         sds.append(sd2)
     return sds
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Vision tower and CLIPModel: the image side of the reference's removal-quality scores (benchmarks/artist_removal.py:
+# 175-194, art_removal.py:80-98 -- transformers' CLIPModel.get_image_features / get_text_features).
+
+@dataclass
+class CLIPVisionConfig:
+    hidden_size: int = 768
+    intermediate_size: int = 3072
+    num_hidden_layers: int = 12
+    num_attention_heads: int = 12
+    patch_size: int = 32
+    image_size: int = 224
+    projection_dim: int = 512
+    hidden_act: str = "quick_gelu"
+    layer_norm_eps: float = 1e-5
+
+    @property
+    def grid(self):
+        return self.image_size // self.patch_size
+
+    @property
+    def num_positions(self):
+        return 1 + self.grid ** 2
+
+    @staticmethod
+    def vit_b32():
+        """openai/clip-vit-base-patch32 vision tower (the reference's scoring model)."""
+        return CLIPVisionConfig()
+
+    @staticmethod
+    def vit_l14():
+        """openai/clip-vit-large-patch14 vision tower."""
+        return CLIPVisionConfig(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16,
+                                patch_size=14, projection_dim=768)
+
+    @staticmethod
+    def tiny(width=128, layers=2, heads=2, patch=4, image=28, projection_dim=64, act="quick_gelu"):
+        return CLIPVisionConfig(hidden_size=width, intermediate_size=4 * width, num_hidden_layers=layers,
+                                num_attention_heads=heads, patch_size=patch, image_size=image,
+                                projection_dim=projection_dim, hidden_act=act)
+
+
+def clip_vision_param_specs(cfg: CLIPVisionConfig):
+    """[(name, shape)] of the vision side of transformers' CLIPModel (checkpoint naming, `pre_layrnorm` sic)."""
+    C, F, p = cfg.hidden_size, cfg.intermediate_size, cfg.patch_size
+    s = [("vision_model.embeddings.class_embedding", (C,)),
+         ("vision_model.embeddings.patch_embedding.weight", (C, 3, p, p)),
+         ("vision_model.embeddings.position_embedding.weight", (cfg.num_positions, C)),
+         ("vision_model.pre_layrnorm.weight", (C,)), ("vision_model.pre_layrnorm.bias", (C,))]
+    for i in range(cfg.num_hidden_layers):
+        q = f"vision_model.encoder.layers.{i}"
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            s += [(f"{q}.self_attn.{n}.weight", (C, C)), (f"{q}.self_attn.{n}.bias", (C,))]
+        s += [(f"{q}.layer_norm1.weight", (C,)), (f"{q}.layer_norm1.bias", (C,)),
+              (f"{q}.mlp.fc1.weight", (F, C)), (f"{q}.mlp.fc1.bias", (F,)),
+              (f"{q}.mlp.fc2.weight", (C, F)), (f"{q}.mlp.fc2.bias", (C,)),
+              (f"{q}.layer_norm2.weight", (C,)), (f"{q}.layer_norm2.bias", (C,))]
+    s += [("vision_model.post_layernorm.weight", (C,)), ("vision_model.post_layernorm.bias", (C,)),
+          ("visual_projection.weight", (cfg.projection_dim, C))]
+    return s
+
+
+def make_clip_vision_state_dict(cfg: CLIPVisionConfig, seed: int = 0):
+    """Random-init fp32 weights of the vision tower (no checkpoints offline), seeded; scales as make_clip_state_dict
+    (class / position embeddings 0.02 / 0.01, linear and patch-conv std 1/sqrt(fan_in), LayerNorm near identity)."""
+    g = torch.Generator().manual_seed(int(seed) + 104729)
+    sd = {}
+    for name, shape in clip_vision_param_specs(cfg):
+        if name.endswith("class_embedding"):
+            t = torch.randn(shape, generator=g) * 0.02
+        elif name.endswith("position_embedding.weight"):
+            t = torch.randn(shape, generator=g) * 0.01
+        elif ("layer_norm" in name or "layernorm" in name or "layrnorm" in name) and name.endswith("weight"):
+            t = 1.0 + 0.05 * torch.randn(shape, generator=g)
+        elif name.endswith("bias"):
+            t = 0.02 * torch.randn(shape, generator=g)
+        else:
+            fan_in = 1
+            for d in shape[1:]:
+                fan_in *= d
+            t = torch.randn(shape, generator=g) / fan_in ** 0.5
+        sd[name] = t
+    return sd
+
+
+class CLIPVisionEmbeddings(nn.Module):
+    """class_embedding [C], position_embedding.weight [1 + G^2, C] and the patch conv as the GEMM weight
+    patch_embedding.weight [C, Kpad] (the conv weight [C, 3, p, p] flattened, K zero-padded to a multiple of 64)."""
+
+    def __init__(self, cls, patch_w, pos):
+        super().__init__()
+        self.class_embedding = _buf(cls)
+        self.patch_embedding = nn.Module()
+        self.patch_embedding.weight = _buf(patch_w)
+        self.position_embedding = nn.Module()
+        self.position_embedding.weight = _buf(pos)
+
+
+class CLIPVisionTransformer(nn.Module):
+    def __init__(self, embeddings, pre_ln, encoder, post_ln):
+        super().__init__()
+        self.embeddings = embeddings
+        self.pre_layrnorm = pre_ln
+        self.encoder = encoder
+        self.post_layernorm = post_ln
+
+
+class CLIPVisionModel(nn.Module):
+    """transformers' CLIPVisionModelWithProjection on the HIP kernels (weights fp16 on `device`). Its input is the
+    patch GEMM's A operand (ops.clip_preprocess), not a pixel_values tensor."""
+
+    def __init__(self, cfg: CLIPVisionConfig, transformer: CLIPVisionTransformer, visual_projection):
+        super().__init__()
+        self.config = cfg
+        self.vision_model = transformer
+        self.visual_projection = visual_projection
+        self._idx = {}
+
+    @classmethod
+    def from_state_dict(cls, sd, cfg: CLIPVisionConfig, device="cuda"):
+        def T(n):
+            return sd[n].to(device=device, dtype=torch.float16).contiguous()
+
+        def lin(p, bias=True):
+            return LoRACompatibleLinear(T(p + ".weight"), T(p + ".bias") if bias else None)
+
+        def ln(p):
+            return _LayerNorm(T(p + ".weight"), T(p + ".bias"), cfg.layer_norm_eps)
+
+        C, p = cfg.hidden_size, cfg.patch_size
+        if cfg.image_size % p:
+            raise ValueError(f"patch size {p} does not divide image size {cfg.image_size}")
+        K, kpad = 3 * p * p, ops.clip_padded_k(p)
+        pw = torch.zeros((C, kpad), dtype=torch.float16, device=device)
+        pw[:, :K] = T("vision_model.embeddings.patch_embedding.weight").reshape(C, K)
+        emb = CLIPVisionEmbeddings(T("vision_model.embeddings.class_embedding"), pw,
+                                   T("vision_model.embeddings.position_embedding.weight"))
+        layers = []
+        for i in range(cfg.num_hidden_layers):
+            q = f"vision_model.encoder.layers.{i}"
+            a = CLIPVisionAttention(*(lin(f"{q}.self_attn.{n}") for n in ("q_proj", "k_proj", "v_proj", "out_proj")),
+                                    cfg.num_attention_heads)
+            mlp = CLIPMLP(lin(f"{q}.mlp.fc1"), lin(f"{q}.mlp.fc2"), cfg.hidden_act)
+            layers.append(CLIPEncoderLayer(a, ln(f"{q}.layer_norm1"), mlp, ln(f"{q}.layer_norm2")))
+        vt = CLIPVisionTransformer(emb, ln("vision_model.pre_layrnorm"), CLIPEncoder(layers),
+                                   ln("vision_model.post_layernorm"))
+        return cls(cfg, vt, lin("visual_projection", bias=False))
+
+    @property
+    def device(self):
+        return self.vision_model.embeddings.class_embedding.device
+
+    def _rows_idx(self, B):
+        """Gather indices of B images over the table [B * G^2 patch rows ; class row]: per image the class row, then
+        its patch rows (CLIPVisionEmbeddings' cat order); and the class-token rows of the stream."""
+        hit = self._idx.get(B)
+        if hit is None:
+            G2, L = self.config.grid ** 2, self.config.num_positions
+            idx = torch.empty((B, L), dtype=torch.int32)
+            idx[:, 0] = B * G2
+            idx[:, 1:] = torch.arange(B * G2, dtype=torch.int32).view(B, G2)
+            cls_rows = torch.arange(B, dtype=torch.int32) * L
+            hit = self._idx[B] = (idx.reshape(-1).to(self.device), cls_rows.to(self.device))
+        return hit
+
+    def encode(self, a_operand, *, hidden=False):
+        """a_operand fp16 [B * G^2, Kpad] (ops.clip_preprocess) -> {"image_embeds": [B, projection_dim], "pooled":
+        post-layernormed class rows [B, C]} (+ "hidden": last_hidden_state [B * (1 + G^2), C] when asked)."""
+        cfg, vm = self.config, self.vision_model
+        G2, L, C = cfg.grid ** 2, cfg.num_positions, cfg.hidden_size
+        M = a_operand.shape[0]
+        if M % G2 or a_operand.shape[1] != vm.embeddings.patch_embedding.weight.shape[1]:
+            raise ValueError(f"a_operand {tuple(a_operand.shape)} is not [B * {G2}, "
+                             f"{vm.embeddings.patch_embedding.weight.shape[1]}]")
+        B = M // G2
+        dev = self.device
+        table = torch.empty((M + 1, C), dtype=torch.float16, device=dev)
+        ops.linear(a_operand, vm.embeddings.patch_embedding.weight, out=table[:M])
+        table[M].copy_(vm.embeddings.class_embedding)
+        idx, cls_rows = self._rows_idx(B)
+        emb = ops.gather_rows(table, idx, add=vm.embeddings.position_embedding.weight, period=L)
+        x = vm.pre_layrnorm.run(emb)
+        scratch = torch.empty((B * L, C), dtype=torch.float16, device=dev)
+        for layer in vm.encoder.layers:
+            layer.run(x, scratch, x, B, L)
+        pooled = vm.post_layernorm.run(ops.gather_rows(x, cls_rows))
+        res = {"pooled": pooled, "image_embeds": self.visual_projection.run(pooled)}
+        if hidden:
+            res["hidden"] = x
+        return res
+
+
+class CLIPModel(nn.Module):
+    """transformers' CLIPModel surface used by the reference's scorers: get_text_features / get_image_features."""
+
+    def __init__(self, text: CLIPTextModel, vision: CLIPVisionModel):
+        super().__init__()
+        if not text.config.projection_dim or text.config.projection_dim != vision.config.projection_dim:
+            raise ValueError("CLIPModel needs text and vision towers with the same projection_dim")
+        self.text_model = text
+        self.vision_model = vision
+
+    @classmethod
+    def from_state_dict(cls, sd, text_cfg: CLIPTextConfig, vision_cfg: CLIPVisionConfig, device="cuda"):
+        return cls(CLIPTextModel.from_state_dict(sd, text_cfg, device),
+                   CLIPVisionModel.from_state_dict(sd, vision_cfg, device))
+
+    @property
+    def device(self):
+        return self.vision_model.device
+
+    def get_text_features(self, input_ids):
+        """Projected pooled text embeddings fp16 [n, projection_dim]."""
+        return self.text_model.encode(input_ids, pooled=True)["text_embeds"]
+
+    def get_image_features(self, a_operand):
+        """Projected image embeddings fp16 [B, projection_dim] of a preprocessed batch (ops.clip_preprocess /
+        sdmoe.scoring.ClipScorer.preprocess)."""
+        return self.vision_model.encode(a_operand)["image_embeds"]

@@ -1157,6 +1157,173 @@ def noise_distance(a, b, nimg, *, img_group=None, ngroups=1, out=None, workspace
     return out
 
 
+CLIP_IMAGE_MEAN = (0.48145466, 0.4578275, 0.40821073)   # transformers OPENAI_CLIP_MEAN / OPENAI_CLIP_STD
+CLIP_IMAGE_STD = (0.26862954, 0.26130258, 0.27577711)
+_RESAMPLE_BITS = 22  # Pillow's 8bpc PRECISION_BITS
+
+
+def clip_quantise(x, out=None):
+    """[B, 3, H, W] fp16 / fp32 in [0, 1] (output_type='pt') -> [B, H, W, 3] uint8, rint(x * 255) half-even, clamped:
+    diffusers' numpy_to_pil on the device (sdmoe_clip_quantise)."""
+    lib = _lib.load()
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"clip_quantise: expected [B, 3, H, W], got {tuple(x.shape)}")
+    if x.dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"clip_quantise: expected float16 or float32, got {x.dtype}")
+    xp = _dev(x, "x", x.dtype)
+    B, _, H, W = x.shape
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=x.device)
+    elif tuple(out.shape) != (B, H, W, 3):
+        raise ValueError(f"clip_quantise: out {tuple(out.shape)} is not {(B, H, W, 3)}")
+    st = lib.sdmoe_clip_quantise(xp, int(x.dtype == torch.float32), B, H, W, _dev(out, "out", torch.uint8), _stream())
+    _lib.check(st, "sdmoe_clip_quantise")
+    return out
+
+
+def _bicubic(x):
+    """Pillow's bicubic_filter (a = -0.5)."""
+    a = -0.5
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def clip_resample_coeffs(in_size: int, out_size: int, first: int = 0, count: int | None = None):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for outputs [first, first + count) of a bicubic resize of
+    one axis from in_size to out_size, in float64 scalar arithmetic in Pillow's operation order: (bounds, kk, ksize),
+    bounds = [(first tap, taps)], kk = rows of ksize 22-bit fixed-point integer weights (zero past the taps)."""
+    count = out_size - first if count is None else count
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ksize = int(-(-support // 1)) * 2 + 1
+    ss = 1.0 / fs
+    bounds, kk = [], []
+    for i in range(first, first + count):
+        center = (i + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size)
+        n = xmax - xmin
+        w = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(n)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        row = [int(v * (1 << _RESAMPLE_BITS) - 0.5) if v < 0 else int(v * (1 << _RESAMPLE_BITS) + 0.5) for v in w]
+        bounds.append((xmin, n))
+        kk.append(row + [0] * (ksize - n))
+    return bounds, kk, ksize
+
+
+def clip_resize_shape(H: int, W: int, size: int):
+    """transformers' CLIP resize: the shortest edge to `size`, the long edge to int(size * long / short)."""
+    short, long = (H, W) if H <= W else (W, H)
+    new_long = int(size * long / short)
+    return (size, new_long) if H <= W else (new_long, size)
+
+
+class ClipResamplePlan:
+    """Device tables of the resize (shortest edge -> S) + centre crop S x S of H x W images: only the crop window's
+    columns and rows, and the input rows [row0, row0 + nrows) the vertical pass reads."""
+
+    def __init__(self, H, W, S, device):
+        oh, ow = clip_resize_shape(H, W, S)
+        self.H, self.W, self.S = H, W, S
+        self.top, self.left = (oh - S) // 2, (ow - S) // 2
+        bx, kx, self.ksx = clip_resample_coeffs(W, ow, self.left, S)
+        by, ky, self.ksy = clip_resample_coeffs(H, oh, self.top, S)
+        self.row0 = min(lo for lo, _ in by)
+        self.nrows = max(lo + n for lo, n in by) - self.row0
+        if min(lo for lo, _ in bx) < 0 or max(lo + n for lo, n in bx) > W or self.row0 < 0 \
+                or self.row0 + self.nrows > H:
+            raise ValueError("clip resample table outside the image")
+
+        def dev(rows):
+            return torch.tensor(rows, dtype=torch.int32).to(device).contiguous()
+
+        self.bx, self.kx, self.by, self.ky = dev(bx), dev(kx), dev(by), dev(ky)
+
+
+_CLIP_PLANS = {}
+
+
+def clip_resample_plan(H, W, S, device) -> ClipResamplePlan:
+    key = (int(H), int(W), int(S), str(device))
+    plan = _CLIP_PLANS.get(key)
+    if plan is None:
+        plan = _CLIP_PLANS[key] = ClipResamplePlan(int(H), int(W), int(S), device)
+    return plan
+
+
+def clip_padded_k(patch: int) -> int:
+    """3 * patch^2 padded up to the patch GEMM's K granule (64)."""
+    return -(-3 * patch * patch // 64) * 64
+
+
+def clip_preprocess(u8, size: int, patch: int = 0, *, a_out=None, u8_out=None, mean=CLIP_IMAGE_MEAN,
+                    std=CLIP_IMAGE_STD):
+    """CLIPImageProcessor on the device for u8 [B, H, W, 3] uint8: Pillow-exact bicubic resize (shortest edge -> size),
+    centre crop size x size (sdmoe_clip_resample_h / _v). a_out: fp16 [B * (size / patch)^2, >= clip_padded_k(patch)]
+    row view that receives the normalised, patchified pixels (the patch GEMM's A operand, padding columns zero);
+    u8_out: uint8 [B, size, size, 3] that receives the cropped pixels. Returns (a_out, u8_out)."""
+    lib = _lib.load()
+    if u8.dim() != 4 or u8.shape[3] != 3:
+        raise ValueError(f"clip_preprocess: expected [B, H, W, 3] uint8, got {tuple(u8.shape)}")
+    if a_out is None and u8_out is None:
+        raise ValueError("clip_preprocess: nothing to write (a_out and u8_out are both None)")
+    up = _dev(u8, "u8", torch.uint8)
+    B, H, W, _ = u8.shape
+    S = int(size)
+    plan = clip_resample_plan(H, W, S, u8.device)
+    ap, lda, kpad = None, 0, 0
+    if a_out is not None:
+        if patch <= 0 or S % patch:
+            raise ValueError(f"clip_preprocess: patch {patch} does not divide size {S}")
+        kpad = clip_padded_k(patch)
+        ap, lda = _rows(a_out, "a_out")
+        if a_out.shape[0] != B * (S // patch) ** 2 or a_out.shape[1] != kpad:
+            raise ValueError(f"clip_preprocess: a_out {tuple(a_out.shape)} is not {(B * (S // patch) ** 2, kpad)}")
+    if u8_out is not None and tuple(u8_out.shape) != (B, S, S, 3):
+        raise ValueError(f"clip_preprocess: u8_out {tuple(u8_out.shape)} is not {(B, S, S, 3)}")
+    uop = None if u8_out is None else _dev(u8_out, "u8_out", torch.uint8)
+    tmp = torch.empty((B, plan.nrows, S, 3), dtype=torch.uint8, device=u8.device)
+    st = lib.sdmoe_clip_resample_h(up, H * W * 3, B, H, W, plan.row0, plan.nrows, plan.bx.data_ptr(),
+                                   plan.kx.data_ptr(), plan.ksx, S, tmp.data_ptr(), _stream())
+    _lib.check(st, "sdmoe_clip_resample_h")
+    f3 = ctypes.c_float * 3
+    st = lib.sdmoe_clip_resample_v(tmp.data_ptr(), B, plan.row0, plan.nrows, plan.by.data_ptr(), plan.ky.data_ptr(),
+                                   plan.ksy, S, int(patch) if a_out is not None else 0, f3(*mean), f3(*std), uop, ap,
+                                   lda, kpad, _stream())
+    _lib.check(st, "sdmoe_clip_resample_v")
+    return a_out, u8_out
+
+
+def clip_scores(T, A, R, out=None):
+    """Removal-quality cosines of fp16 feature rows T (text; None), A (original), R (removal) [n, D]
+    (sdmoe_clip_scores): device float64 [3 n + 3] = cos(T,A) | cos(T,R) | cos(A,R) | sum cos(A,R), sum cos(A,R)^2,
+    count of cos(T,A) > cos(T,R). float64, fixed order: bit-identical from run to run."""
+    lib = _lib.load()
+    ap, lda = _rows(A, "A")
+    rp, ldr = _rows(R, "R")
+    tp, ldt = (None, 0) if T is None else _rows(T, "T")
+    n, D = A.shape
+    if R.shape != A.shape or (T is not None and T.shape != A.shape):
+        raise ValueError("clip_scores: T, A and R must have the same [n, D] shape")
+    if out is None:
+        out = torch.empty(3 * n + 3, dtype=torch.float64, device=A.device)
+    elif out.numel() != 3 * n + 3:
+        raise ValueError(f"clip_scores: out has {out.numel()} values, expected {3 * n + 3}")
+    st = lib.sdmoe_clip_scores(tp, ldt, ap, lda, rp, ldr, n, D, _dev(out, "out", torch.float64), _stream())
+    _lib.check(st, "sdmoe_clip_scores")
+    return out
+
+
 def expert_mean_topk(score, k: int, rows_per_img: int = 0, row_idx=None, mean_out=None, topk_out=None):
     """GetExperts statistic (get_experts.py:72-80): mean of the fp16 expert scores [M, E] over all tokens, or
     over positions row_idx (int32 device tensor) of every rows_per_img-row image, then the top-k expert ids

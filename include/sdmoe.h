@@ -544,6 +544,42 @@ int sdmoe_noise_distance(const void* a, long lda, long step_a, const void* b, lo
                          long workspace_doubles, void* stream);
 
 /*
+ * The CLIP removal-quality scorer's image front end and score reduction (csrc/clip_image.hip). Replaces: the PNG
+ * round trip, CLIPProcessor's host-side Pillow bicubic resize / centre crop / normalise and the per-image fp32
+ * cosines of benchmarks/artist_removal.py:182-207 and benchmarks/art_removal.py:80-98, 114-125.
+ * sdmoe_clip_quantise: x [B, 3, H, W] fp16 (is_fp32 == 0) or fp32, contiguous -> out [B, H, W, 3] uint8,
+ *   rint(float(x) * 255.0f) round-half-even, clamped to [0, 255] (NaN -> 0). Replaces diffusers' numpy_to_pil
+ *   ((images * 255).round().astype("uint8")).
+ * sdmoe_clip_resample_h / _v: Pillow's 8-bit bicubic resampler (libImaging/Resample.c), horizontal pass then
+ *   vertical pass with a uint8 intermediate, restricted to the centre-crop window. A pass's table is `bounds` int32
+ *   [S, 2] = (first tap, taps) and `kk` int32 [S, ksize] 22-bit fixed-point weights, device memory, built on the host
+ *   exactly as precompute_coeffs / normalize_coeffs_8bpc do, for the S outputs inside the crop window; an output is
+ *   clip8((2^21 + sum pixel * k) >> 22) in int32. The caller guarantees every tap range lies inside the image
+ *   (horizontal: [0, W)) or inside rows [row0, row0 + nrows) (vertical).
+ *   _h: in uint8 [B, H, W, 3] (image b at in + b * in_bstride bytes) -> tmp uint8 [B, nrows, S, 3], input rows
+ *     [row0, row0 + nrows).
+ *   _v: tmp -> u8out uint8 [B, S, S, 3] (optional) and A (optional): fp16 ((u8 * (1/255)) - mean[c]) / std[c],
+ *     each step rounded in fp32, at row b G^2 + py G + px (G = S / patch, row stride lda), column
+ *     c patch^2 + iy patch + ix -- the flattening of the patch-embedding conv weight [D, 3, patch, patch] -- with
+ *     columns [3 patch^2, kpad) written as zero (kpad <= lda; the patch GEMM's K padded to a multiple of 64). mean,
+ *     std: 3 host floats. Replaces CLIPImageProcessor.resize / center_crop / rescale / normalize and the unfold of
+ *     CLIPVisionEmbeddings.patch_embedding; no fp32 pixel_values tensor exists.
+ * sdmoe_clip_scores: T (may be NULL), A, R fp16 [n, D] feature rows (text, original image, removal image; row
+ *   strides ldt, lda, ldr) -> out float64 [3 n + 3]: out[i] = cos(T,A), out[n + i] = cos(T,R), out[2 n + i] =
+ *   cos(A,R) of row i, cos(x,y) = x.y / (max(|x|, 1e-8) max(|y|, 1e-8)) (torch.nn.functional.cosine_similarity;
+ *   0 for the text cosines without T), then out[3 n ..] = sum cos(A,R), sum cos(A,R)^2, count of cos(T,A) > cos(T,R).
+ *   float64 throughout, fixed summation order, no atomics: bit-identical from run to run. out 8-byte aligned.
+ */
+int sdmoe_clip_quantise(const void* x, int is_fp32, int B, int H, int W, void* out, void* stream);
+int sdmoe_clip_resample_h(const void* in, long in_bstride, int B, int H, int W, int row0, int nrows,
+                          const int* bounds, const int* kk, int ksize, int S, void* tmp, void* stream);
+int sdmoe_clip_resample_v(const void* tmp, int B, int row0, int nrows, const int* bounds, const int* kk, int ksize,
+                          int S, int patch, const float* mean, const float* std, void* u8out, void* A, long lda,
+                          int kpad, void* stream);
+int sdmoe_clip_scores(const void* T, long ldt, const void* A, long lda, const void* R, long ldr, int n, int D,
+                      double* out, void* stream);
+
+/*
  * Tuning knobs for A/B experiments: process-wide integers the launch code reads. Ids, legal values and defaults are
  * ABI (recorded command lines name them). This is the one definition of what each value means; the library's table
  * (csrc/tune.hip) holds id, name, default and legal set. sdmoe_tune returns -1 for an unknown knob or an illegal
