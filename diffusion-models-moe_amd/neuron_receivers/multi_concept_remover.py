@@ -12,6 +12,8 @@ PIL paste at :83-99 (latents, or RGB when the pipeline decodes) -- and `singles`
 one concept). The unstitched images of the last call are kept in `self.last_outputs`.
 remove_concepts_batch (not in the reference) runs the removal of a whole batch of prompts, each with its own concept
 list, in one pipeline call: the loop of benchmarks/unified_editing.py:106-126 as one batched call.
+remove_concepts_routed does the same from the prompts alone: a sdmoe.concepts.ConceptRouter (the concept checkers of
+benchmarks/concept_checkers.py on the device) decides each prompt's concepts inside the call.
 """
 from __future__ import annotations
 
@@ -80,17 +82,38 @@ class MultiConceptRemoverWanda:
         exactly concepts_per_prompt[i] (an empty list = the unedited image), through WandaRemovePerPrompt. Returns the
         list of removal images in prompt order. Prompt i starts from the latents of global prompt index
         model.prompt_offset + i, as any batched call. The shared union remover is neither used nor changed."""
-        from neuron_receivers.remove_wanda_per_prompt import WandaRemovePerPrompt
         prompts = [prompts] if isinstance(prompts, str) else list(prompts)
         if len(prompts) != len(concepts_per_prompt):
             raise ValueError(f"{len(prompts)} prompts but {len(concepts_per_prompt)} concept lists")
-        rec = self.per_prompt_remover
-        if rec is None or list(rec.removers.values()) != list(self.removers.values()):
-            rec = self.per_prompt_remover = WandaRemovePerPrompt(self.removers, seed=self.seed, store_gates=False)
+        rec = self._per_prompt()
         rec.set_prompt_concepts(concepts_per_prompt)
         rec.reset_time_layer()
         out, _ = rec.observe_activation(model, prompts)
         return list(out)
+
+    def _per_prompt(self):
+        from neuron_receivers.remove_wanda_per_prompt import WandaRemovePerPrompt
+        rec = self.per_prompt_remover
+        if rec is None or list(rec.removers.values()) != list(self.removers.values()):
+            rec = self.per_prompt_remover = WandaRemovePerPrompt(self.removers, seed=self.seed, store_gates=False)
+        return rec
+
+    def remove_concepts_routed(self, model, prompts, router):
+        """remove_concepts_batch with the concept lists decided on the device: router (sdmoe.concepts.ConceptRouter)
+        is bound to this remover's concept order, its select words for the call's prompts go straight into the
+        per-prompt unions. Returns (removal images in prompt order, the int32 device tensor of select words;
+        router.names(select) decodes it for a results file)."""
+        prompts = [prompts] if isinstance(prompts, str) else list(prompts)
+        router.bind(list(self.removers))
+        rec = self._per_prompt()
+        rec.router = router
+        rec.clear_prompt_sets()
+        rec.reset_time_layer()
+        try:
+            out, _ = rec.observe_activation(model, prompts)
+        finally:
+            rec.router = None
+        return list(out), rec.last_select
 
     def remove_concepts(self, model, prompt, concepts):
         """Returns (stitched [original | union removed], per-concept stitched pairs or None) -- two values, as the

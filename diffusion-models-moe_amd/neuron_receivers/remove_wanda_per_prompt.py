@@ -27,6 +27,13 @@ WandaRemoveNeuronsFast.device_kmajor, written into the stack so no second per-re
 as the packed bits again: 316 MB per concept for SD-1.4 at T = 51, on top of the removers' own 316 MB each. The
 union buffer is nsets masks of the largest layer (0.8 MB each for SD-1.4).
 
+set_prompt_select() takes the call's select words as a device tensor instead (sdmoe.concepts.ConceptRouter writes
+them): one set per prompt, the identity image table, no host copy and no dedupe -- which costs nsets = B unions per
+hooked call instead of the number of distinct sets. With router= and no sets configured, observe_activation registers
+a prompt hook for the call (StableDiffusionPipeline.register_prompt_hook): on an SD-1.x pipeline whose text encoder is
+the router's own the router reads the conditional rows encode_prompt just wrote, otherwise (SDXL, synthetic
+conditioning, another encoder) it encodes the prompts itself; either way the words go from sdmoe_concept_route straight into the union launch.
+
 hook_module='unet' only: the text-encoder variant and the GEGLU-gate variant raise SdmoeError.
 """
 from __future__ import annotations
@@ -47,7 +54,7 @@ MAX_CONCEPTS = 32
 class WandaRemovePerPrompt(NeuronPredictivity):
     _sdmoe_fused_nimg = True  # sdmoe.unet.FeedForward passes fused_linear the call's image count
 
-    def __init__(self, removers, seed=0, replace_fn=GEGLU, keep_nsfw=False, hook_module='unet', **kw):
+    def __init__(self, removers, seed=0, replace_fn=GEGLU, keep_nsfw=False, hook_module='unet', router=None, **kw):
         removers = dict(removers)
         if not removers:
             raise SdmoeError("WandaRemovePerPrompt needs at least one concept remover")
@@ -64,6 +71,9 @@ class WandaRemovePerPrompt(NeuronPredictivity):
         self.removers = removers
         self.concepts = list(removers)
         self.sets, self.select, self.prompt_sets = [], [], []
+        self.router = router     # sdmoe.concepts.ConceptRouter or None: routes a call that has no sets configured
+        self._select_dev = None  # set_prompt_select: the call's select words, on the device
+        self.last_select = None  # the select words the router wrote for the last routed call
         self._dev = {}     # ("stack", t, l, perm is None) -> (perm, the removers' packed masks, stacked device masks)
         self._tables = {}  # per-call device state: the select words, image tables by image count, union buffers
 
@@ -87,8 +97,31 @@ class WandaRemovePerPrompt(NeuronPredictivity):
         self.sets = sets
         self.select = [sum(1 << index[c] for c in s) for s in sets]
         self.prompt_sets = ids
+        self._select_dev = None
         self._tables = {}
         return ids
+
+    def set_prompt_select(self, select_dev):
+        """Fix the next call's sets from select words already on the device (int32 [B], bit patterns of uint32 words,
+        bit c = concept number c): one set per prompt, in prompt order, the identity image table [0..B-1] (twice over
+        under guidance). The words are used as they are: no host copy, no dedupe, so every hooked call makes B unions
+        where set_prompt_concepts makes one per distinct set."""
+        if not isinstance(select_dev, torch.Tensor) or select_dev.dtype != torch.int32 or select_dev.dim() != 1 \
+                or select_dev.numel() == 0:
+            raise SdmoeError("set_prompt_select takes an int32 device tensor [B >= 1] of select words")
+        if not select_dev.is_cuda:
+            raise SdmoeError("set_prompt_select: the select words are not on a GPU device")
+        B = select_dev.numel()
+        self.sets, self.select = None, None
+        self.prompt_sets = list(range(B))
+        self._select_dev = select_dev.contiguous()
+        self._tables = {}
+        return self.prompt_sets
+
+    def clear_prompt_sets(self):
+        self.sets, self.select, self.prompt_sets = [], [], []
+        self._select_dev = None
+        self._tables = {}
 
     def image_table(self, nimg):
         """Set id of each of the call's nimg U-Net images: the prompts' ids, twice over ([uncond x B ; cond x B]) under
@@ -125,7 +158,7 @@ class WandaRemovePerPrompt(NeuronPredictivity):
 
     def _call_state(self, nimg, shape, device):
         """(select words on the device, host image table, its device copy, union buffer [nsets, *shape])."""
-        sel = self._tables.get(("select", device))
+        sel = self._select_dev if self._select_dev is not None else self._tables.get(("select", device))
         if sel is None:
             words = np.array(self.select, dtype=np.uint32).view(np.int32)
             sel = self._tables[("select", device)] = torch.from_numpy(words.copy()).to(device)
@@ -135,7 +168,7 @@ class WandaRemovePerPrompt(NeuronPredictivity):
             tab = self._tables[("table", nimg, device)] = (host, torch.tensor(host, dtype=torch.int32, device=device))
         buf = self._tables.get(("union", shape, device))
         if buf is None:
-            buf = self._tables[("union", shape, device)] = torch.empty((len(self.select),) + shape, dtype=torch.int64,
+            buf = self._tables[("union", shape, device)] = torch.empty((sel.numel(),) + shape, dtype=torch.int64,
                                                                       device=device)
         return sel, tab[0], tab[1], buf
 
@@ -191,8 +224,33 @@ class WandaRemovePerPrompt(NeuronPredictivity):
     def register_hooks(self, model, bboxes=None):
         return [self._register(m, self.linear_hook_fn) for _, m in self.hook_modules(model)]
 
+    def _route_hook(self, model):
+        """The prompt hook of a routed call: the router's select words for the call's prompts -> set_prompt_select."""
+        from sdmoe.unet import CTX_LEN
+
+        def hook(prompts, ctx, B):
+            router = self.router
+            if router.row_bit is None or router.concept_names != self.concepts:
+                router.bind(self.concepts)
+            # the conditional rows are the checkers' rows only when the router's bank came from the same encoder
+            if model.text_encoder is not None and not model.is_sdxl and model.text_encoder is router.text_encoder:
+                sel = router.select_from_hidden(ctx[B * CTX_LEN:], B, prompts)
+            else:
+                sel = router.select(prompts)
+            self.last_select = sel
+            self.set_prompt_select(sel)
+        return hook
+
     def observe_activation(self, model, ann, bboxes=None):
         prompts = [ann] if isinstance(ann, str) else list(ann)
+        if self.router is not None and not self.prompt_sets:
+            handle = model.register_prompt_hook(self._route_hook(model))
+            self.prepare(model)
+            try:
+                return super().observe_activation(model, ann, bboxes)
+            finally:
+                handle.remove()
+                self.clear_prompt_sets()
         if len(prompts) != len(self.prompt_sets):
             raise SdmoeError(f"the call has {len(prompts)} prompts, set_prompt_concepts configured "
                              f"{len(self.prompt_sets)}")

@@ -70,6 +70,8 @@ SIGNATURES = {
     "sdmoe_clip_resample_h": [_P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P],
     "sdmoe_clip_resample_v": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _FP, _FP, _P, _P, _L, _I, _P],
     "sdmoe_clip_scores": [_P, _L, _P, _L, _P, _L, _I, _I, _P, _P],
+    "sdmoe_text_pool": [_P, _L, _I, _I, _I, _I, _I, _P, _L, _P],
+    "sdmoe_concept_route": [_P, _L, _I, _I, _I, _P, _L, _I, _P, _P, _I, _P, _P, _P, _P],
     "sdmoe_softmax_rows": [_P, _L, _P, _L, _I, _I, _P],
     "sdmoe_transpose": [_P, _L, _P, _L, _I, _I, _P],
     "sdmoe_gather_rows": [_P, _L, _P, _I, _I, _P, _L, _I, _P, _L, _P],

@@ -1324,6 +1324,102 @@ def clip_scores(T, A, R, out=None):
     return out
 
 
+POOL_MAX_D = 2048  # sdmoe_text_pool / sdmoe_concept_route: 256 chunks of 8 columns
+
+
+def _pool_rows(X, nseq, name):
+    """(ptr, row stride, L, D) of fp16 hidden-state rows [nseq * L, D] (a row-strided or offset view is fine)."""
+    xp, ldx = _rows(X, name)
+    rows, D = X.shape
+    if nseq <= 0 or rows % nseq or rows == 0:
+        raise ValueError(f"{name}: {rows} rows are not {nseq} whole sequences")
+    if not 1 <= D <= POOL_MAX_D:
+        raise ValueError(f"{name}: D = {D} is outside 1..{POOL_MAX_D}")
+    return xp, ldx, rows // nseq, D
+
+
+def text_pool(X, nseq, group=1, renorm=False, out=None):
+    """Unit mean features of text-encoder rows (sdmoe_text_pool): X fp16 [nseq * L, D] -> float64 [nseq / group, D];
+    per sequence f = mean of its L rows / its norm (no epsilon: an all-zero block gives NaN), then the mean of every
+    `group` consecutive f, re-normalised if renorm. float64, fixed order: bit-identical from run to run."""
+    xp, ldx, L, D = _pool_rows(X, int(nseq), "X")
+    group = int(group)
+    if group <= 0 or nseq % group:
+        raise ValueError(f"text_pool: {nseq} sequences are not whole groups of {group}")
+    if out is None:
+        out = torch.empty((nseq // group, D), dtype=torch.float64, device=X.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (nseq // group, D):
+        raise ValueError(f"out must be float64 [{nseq // group}, {D}], got {out.dtype} {tuple(out.shape)}")
+    op = _dev(out, "out", torch.float64)
+    st = _lib.load().sdmoe_text_pool(xp, ldx, int(nseq), L, D, group, int(bool(renorm)), op, out.stride(0), _stream())
+    _lib.check(st, "sdmoe_text_pool")
+    return out
+
+
+def concept_groups(groups, R, device=None):
+    """The group table of concept_route from host records (row0, row1, neg_row, anchor_row or -1, threshold or None /
+    -inf), checked against the R bank rows: int32 [G, 6] in sdmoe_concept_group's layout (four ints and the bits of
+    the float64 threshold), on `device` if given."""
+    import numpy as np
+    rec = np.zeros(len(groups), dtype=np.dtype([("rows", "<i4", 4), ("thr", "<f8")]))
+    for g, (row0, row1, neg, anchor, thr) in enumerate(groups):
+        row0, row1, neg, anchor = int(row0), int(row1), int(neg), -1 if anchor is None else int(anchor)
+        if not 0 <= row0 < row1 <= R or not 0 <= neg < R or not -1 <= anchor < R:
+            raise ValueError(f"group {g}: rows ({row0}, {row1}, {neg}, {anchor}) do not fit a bank of {R} rows")
+        rec[g] = ((row0, row1, neg, anchor), float("-inf") if thr is None else float(thr))
+    t = torch.from_numpy(rec.view("<i4").reshape(len(groups), 6).copy())
+    return t if device is None else t.to(device)
+
+
+def concept_route(X, nprompt, bank, row_bit, groups, preset=None, select_out=None, sims_out=None, sims=True):
+    """Per-prompt select words from text-encoder rows in one launch (sdmoe_concept_route). X fp16 [nprompt * L, D];
+    bank float64 [R, D] (text_pool rows); row_bit int32 [R] (the select bit of each bank row, -1 = none): a host
+    sequence (checked here, uploaded) or a device tensor the caller has checked; groups: host records (concept_groups
+    checks and uploads them) or its int32 [G, 6] device tensor; preset: optional int32 [nprompt] words OR-ed in first.
+    Returns (select int32 [nprompt] -- bit patterns of uint32 words, the operand of wmask_union_sets --, sims float64
+    [nprompt, R] or None with sims=False)."""
+    nprompt = int(nprompt)
+    if bank.dim() != 2 or bank.shape[0] < 1 or bank.dtype != torch.float64:
+        raise ValueError(f"bank must be float64 [R >= 1, D], got {bank.dtype} {tuple(bank.shape)}")
+    R = bank.shape[0]
+    # the host forms are checked before anything touches the device
+    if not isinstance(row_bit, torch.Tensor):
+        bits = [int(v) for v in row_bit]
+        if len(bits) != R or any(v < -1 or v > 31 for v in bits):
+            raise ValueError(f"row_bit must hold {R} bits in -1..31, got {bits}")
+        row_bit = torch.tensor(bits, dtype=torch.int32)
+    elif row_bit.dtype != torch.int32 or tuple(row_bit.shape) != (R,):
+        raise ValueError(f"row_bit must be int32 [{R}], got {row_bit.dtype} {tuple(row_bit.shape)}")
+    if not isinstance(groups, torch.Tensor):
+        groups = concept_groups(list(groups), R)
+    elif groups.dtype != torch.int32 or groups.dim() != 2 or groups.shape[1] != 6:
+        raise ValueError(f"groups must be int32 [G, 6] (concept_groups), got {groups.dtype} {tuple(groups.shape)}")
+    xp, ldx, L, D = _pool_rows(X, nprompt, "X")
+    dev = X.device
+    if bank.shape[1] != D or (bank.stride(1) != 1 and D > 1) or not bank.is_cuda:
+        raise ValueError(f"bank must be a device tensor [R, {D}] with contiguous rows, got {tuple(bank.shape)} on "
+                         f"{bank.device}")
+    row_bit, groups = row_bit.to(dev), groups.to(dev)
+    G = groups.shape[0]
+    if preset is not None and (preset.dtype != torch.int32 or tuple(preset.shape) != (nprompt,)):
+        raise ValueError(f"preset must be int32 [{nprompt}], got {preset.dtype} {tuple(preset.shape)}")
+    if select_out is None:
+        select_out = torch.empty(nprompt, dtype=torch.int32, device=dev)
+    elif select_out.dtype != torch.int32 or tuple(select_out.shape) != (nprompt,):
+        raise ValueError(f"select_out must be int32 [{nprompt}], got {select_out.dtype} {tuple(select_out.shape)}")
+    if sims_out is None and sims:
+        sims_out = torch.empty((nprompt, R), dtype=torch.float64, device=dev)
+    elif sims_out is not None and (sims_out.dtype != torch.float64 or tuple(sims_out.shape) != (nprompt, R)):
+        raise ValueError(f"sims_out must be float64 [{nprompt}, {R}], got {sims_out.dtype} {tuple(sims_out.shape)}")
+    st = _lib.load().sdmoe_concept_route(
+        xp, ldx, nprompt, L, D, bank.data_ptr(), bank.stride(0), R, _dev(row_bit, "row_bit", torch.int32),
+        _dev(groups, "groups", torch.int32) if G else None, G,
+        None if preset is None else _dev(preset, "preset", torch.int32), _dev(select_out, "select_out", torch.int32),
+        None if sims_out is None else _dev(sims_out, "sims_out", torch.float64), _stream())
+    _lib.check(st, "sdmoe_concept_route")
+    return select_out, sims_out
+
+
 def expert_mean_topk(score, k: int, rows_per_img: int = 0, row_idx=None, mean_out=None, topk_out=None):
     """GetExperts statistic (get_experts.py:72-80): mean of the fp16 expert scores [M, E] over all tokens, or
     over positions row_idx (int32 device tensor) of every rows_per_img-row image, then the top-k expert ids

@@ -121,7 +121,8 @@ class PipelineOutput:
 
 
 class _HookHandle:
-    """Returned by StableDiffusionPipeline.register_unet_output_hook: remove() takes the hook off again (once)."""
+    """Returned by StableDiffusionPipeline.register_unet_output_hook / register_prompt_hook: remove() takes the hook
+    off again (once)."""
 
     def __init__(self, hooks, fn):
         self._hooks, self._fn = hooks, fn
@@ -153,6 +154,7 @@ class StableDiffusionPipeline:
         self.text_encoder_2 = text_encoder_2
         self.tokenizer_2 = tokenizer_2
         self._unet_output_hooks = []  # register_unet_output_hook
+        self._prompt_hooks = []  # register_prompt_hook
 
     def register_unet_output_hook(self, fn):
         """Call fn(step_index, eps, nimg, HW) after every U-Net evaluation of the denoising loop, before the scheduler
@@ -164,6 +166,16 @@ class StableDiffusionPipeline:
         value is ignored. Returns a handle whose .remove() unregisters fn."""
         self._unet_output_hooks.append(fn)
         return _HookHandle(self._unet_output_hooks, fn)
+
+    def register_prompt_hook(self, fn):
+        """Call fn(prompts, ctx, B) in every __call__ after encode_prompt and before the denoising loop: prompts the
+        call's B prompt strings, ctx the full fp16 [2B * 77, dim] conditioning buffer ([uncond x B ; cond x B] rows,
+        also when the call runs without guidance and the loop reads only the conditional half). The seam of the
+        reference's per-prompt concept checkers (benchmarks/unified_editing.py:109-119): a hook may configure a
+        receiver for the call from the rows (neuron_receivers.WandaRemovePerPrompt with a router). The return value
+        is ignored. Returns a handle whose .remove() unregisters fn."""
+        self._prompt_hooks.append(fn)
+        return _HookHandle(self._prompt_hooks, fn)
 
     def _after_unet(self, step_index, eps, HW):
         for fn in tuple(self._unet_output_hooks):
@@ -238,6 +250,8 @@ class StableDiffusionPipeline:
         lat = latents.to(self.device, torch.float32).contiguous()
         ncopy = 2 if do_cfg else 1
         ctx, pooled = self.encode_prompt(prompts, return_pooled=True)
+        for fn in tuple(self._prompt_hooks):
+            fn(prompts, ctx, B)
         add_hidden = None
         if self.is_sdxl:
             ac = self.added_cond(prompts, pooled)

@@ -580,6 +580,48 @@ int sdmoe_clip_scores(const void* T, long ldt, const void* A, long lda, const vo
                       double* out, void* stream);
 
 /*
+ * The concept checkers' decision step on the device (csrc/concepts.hip): from fp16 text-encoder hidden-state rows to
+ * the per-prompt select words of sdmoe_wmask_union_sets, with no host round trip. float64 arithmetic in one fixed
+ * order, no atomics: bit-identical from run to run.
+ * sdmoe_text_pool: X fp16 [nseq * L, D] (row stride ldx) -> out float64 [nseq / group, D] (row stride ldo). Per
+ *   sequence p = mean over its L rows, f = p / |p| (IEEE division, no epsilon: an all-zero block gives NaN, as the
+ *   reference); out[g] = mean of f over sequences g * group .. (g + 1) * group - 1, summed in sequence order and
+ *   divided by group, then out[g] / |out[g]| if renorm. group = 1: a prompt's feature. group = n_objects, renorm = 0:
+ *   one row of embed_all_objects / embed_anchor_prompts; renorm = 1: no_concept_features. The reference normalises
+ *   object_features twice (concept_checkers.py:55, :59): the second pass is a no-op to within an ulp, done once here.
+ *   nseq % group == 0, ldx >= D, ldo >= D (SDMOE_EARG); D <= 2048 (SDMOE_EUNSUP); X 2-byte and out 8-byte aligned
+ *   (SDMOE_ESHAPE). 16-byte loads when X is 16-byte aligned and ldx % 8 == 0, else 2-byte loads.
+ * sdmoe_concept_route: one launch for a batch. Prompt b's feature f_b is pooled from its L rows of X (as above,
+ *   group = 1); sims[b][r] = f_b . bank[r] over the R float64 rows of bank (row stride ldb), every row summed in the
+ *   same lane / column order, so identical bank rows give identical sims; written to sims_out [nprompt, R] if not
+ *   NULL. Then, for each of the G records of `groups` (device memory): m = max of sims[b][row0 .. row1 - 1], r* the
+ *   FIRST row reaching it (Python's max(sim, key=sim.get), concept_checkers.py:174); the group fires iff
+ *   (m > sims[b][neg_row] && m > threshold) || (anchor_row >= 0 && sims[b][anchor_row] > sims[b][neg_row]) --
+ *   strict comparisons, false whenever a NaN is involved (:127-133, :179); threshold = -inf for none. A firing group
+ *   ORs bit row_bit[r*] (device int32 [R], -1 = none: the arg-max concept is unknown to the remover, nothing is removed
+ *   even when the runner-up is known, unified_editing.py:116; rows may share a bit) into select_out[b], which starts
+ *   from preset[b] (device uint32 [nprompt], may be NULL: host-side decisions such as MemorizedPromptChecker.decide,
+ *   :237-241). G == 0 gives select = preset. A record whose rows lie outside [0, R) never fires; a bit outside
+ *   0..31 is ignored. Limits and alignment as sdmoe_text_pool; bank, groups, sims_out 8-byte, the int tables 4-byte
+ *   aligned.
+ * Replaces: ArtStyleChecker.decide / NudityChecker.decide and BaseConceptChecker.similarity / embed_all_objects /
+ *   no_concept_features (benchmarks/concept_checkers.py:32-81, 119-133, 170-184), which run one fp32 CLIP text pass per
+ *   prompt and per checker, and the routing lines of benchmarks/unified_editing.py:106-126 that turn their answers
+ *   into each prompt's concept list on the host.
+ */
+typedef struct sdmoe_concept_group {
+  int row0, row1;   /* the group's bank rows [row0, row1) */
+  int neg_row;      /* the no-concept row */
+  int anchor_row;   /* -1 = none */
+  double threshold; /* -inf = none */
+} sdmoe_concept_group;
+int sdmoe_text_pool(const void* X, long ldx, int nseq, int L, int D, int group, int renorm, double* out, long ldo,
+                    void* stream);
+int sdmoe_concept_route(const void* X, long ldx, int nprompt, int L, int D, const double* bank, long ldb, int R,
+                        const int* row_bit, const sdmoe_concept_group* groups, int G, const unsigned* preset,
+                        unsigned* select_out, double* sims_out, void* stream);
+
+/*
  * Tuning knobs for A/B experiments: process-wide integers the launch code reads. Ids, legal values and defaults are
  * ABI (recorded command lines name them). This is the one definition of what each value means; the library's table
  * (csrc/tune.hip) holds id, name, default and legal set. sdmoe_tune returns -1 for an unknown knob or an illegal
