@@ -79,6 +79,8 @@ SIGNATURES = {
     "sdmoe_timestep_embedding_rows": [_P, _L, _P, _I, _I, _I, _I, _F, _P],
     "sdmoe_prepare_input": [_P, _P, _I, _I, _L, _I, _P],
     "sdmoe_cfg_ddim_step": [_P, _L, _P, _I, _I, _I, _F, _F, _F, _P, _L, _P],
+    "sdmoe_cfg_x0_step": [_P, _L, _P, _I, _I, _I, _F, _P, _P, _P, _P, _L, _P],
+    "sdmoe_prepare_input_scaled": [_P, _P, _I, _I, _L, _I, _F, _F, _P],
     "sdmoe_add": [_P, _P, _P, _L, _P],
     "sdmoe_tune": [_I, _I],
     "sdmoe_tune_knob": [_I, _IP, ctypes.POINTER(ctypes.c_char_p), _IP, _IP],

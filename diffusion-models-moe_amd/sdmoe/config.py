@@ -66,6 +66,15 @@ class UNetConfig:
                           sample_size=sample_size, name="tiny")
 
     @staticmethod
+    def sd2(sample_size: int = 96):
+        """stabilityai/stable-diffusion-2 U-Net (768^2 -> 96^2; stable-diffusion-2-1 is the same U-Net with other
+        weights): SD-1.4's channel and layer structure with 64-wide heads (5, 10, 20, 20 of them), linear proj_in /
+        proj_out and the 1024-wide OpenCLIP-H context. Both checkpoints predict v: run them with
+        StableDiffusionPipeline(..., scheduler="euler" (SD-2) or "dpmpp_2m" (SD-2.1), prediction_type="v_prediction")."""
+        return UNetConfig(head_dim=64, cross_attention_dim=1024, use_linear_projection=True, sample_size=sample_size,
+                          name="sd-2")
+
+    @staticmethod
     def sdxl(sample_size: int = 128):
         """stabilityai/stable-diffusion-xl-base-1.0 U-Net (2.57 B params; 70 GEGLU FFNs; 1024^2 -> 128^2)."""
         return UNetConfig(block_out_channels=(320, 640, 1280),

@@ -1566,6 +1566,40 @@ def cfg_multistep_step(eps: torch.Tensor, lat: torch.Tensor, do_cfg: bool, guida
     return lat
 
 
+def prepare_input_scaled(lat: torch.Tensor, out: torch.Tensor, ncopy: int, lat_scale: float, in_scale: float):
+    """lat *= lat_scale in place (latents * scheduler.init_noise_sigma), then out = fp16(lat * in_scale) for ncopy
+    copies (the first step's scale_model_input): prepare_input for the sigma schedulers."""
+    lib = _lib.load()
+    B, C, H, W = lat.shape
+    op, ldo = _rows(out, "out")
+    st = lib.sdmoe_prepare_input_scaled(_dev(lat, "lat", torch.float32), op, B, H * W, ldo, ncopy, float(lat_scale),
+                                        float(in_scale), _stream())
+    _lib.check(st, "sdmoe_prepare_input_scaled")
+    return out
+
+
+def cfg_x0_step(eps: torch.Tensor, lat: torch.Tensor, do_cfg: bool, guidance: float, prev_x0: torch.Tensor | None,
+                coef, flags, next_in: torch.Tensor | None = None):
+    """CFG + one Euler / DPM-Solver++ 2M update in place (pipeline.euler_schedule / dpmpp_2m_schedule give coef[6] =
+    [cx, cm, a, b0, b1, in_scale] and flags[2] = [use_prev, store_prev] per step). prev_x0 [B, 4, H, W] fp32 may be None
+    when both flags are 0."""
+    import ctypes
+    lib = _lib.load()
+    B, C, H, W = lat.shape
+    if prev_x0 is not None and tuple(prev_x0.shape) != (B, C, H, W):
+        raise ValueError("cfg_x0_step: prev_x0 [B, 4, H, W] expected")
+    ep, lde = _rows(eps, "eps")
+    np_, ldn = (None, 0) if next_in is None else _rows(next_in, "next_in")
+    cf = (ctypes.c_float * 6)(*[float(v) for v in coef])
+    fl = (ctypes.c_int * 2)(*[int(v) for v in flags])
+    pp = None if prev_x0 is None else _dev(prev_x0, "prev_x0", torch.float32)
+    st = lib.sdmoe_cfg_x0_step(ep, lde, _dev(lat, "lat", torch.float32), B, H * W, int(bool(do_cfg)),
+                               float(guidance), pp, ctypes.cast(cf, ctypes.c_void_p),
+                               ctypes.cast(fl, ctypes.c_void_p), np_, ldn, _stream())
+    _lib.check(st, "sdmoe_cfg_x0_step")
+    return lat
+
+
 def softmax_rows(x, out=None):
     """Row softmax of a 2-D fp16 view (fp32 max / sum), sdmoe_softmax_rows."""
     lib = _lib.load()

@@ -1,5 +1,6 @@
-"""StableDiffusionPipeline stand-in: synthetic text conditioning + DDIM + classifier-free guidance, with the
-denoising loop entirely on the GPU (U-Net on the sdmoe kernels, CFG + DDIM update in one HIP kernel).
+"""StableDiffusionPipeline stand-in: synthetic text conditioning + a scheduler (DDIM, PNDM, Euler or DPM-Solver++ 2M;
+epsilon or v-prediction for the last two) + classifier-free guidance, with the denoising loop entirely on the GPU
+(U-Net on the sdmoe kernels, CFG + scheduler update + next U-Net input in one HIP kernel).
 
 Call shape kept from diffusers / the reference's callers: `pipe(prompt_or_list, safety_checker=...)` returns
 an object with `.images` (base_receiver.py:73, remove_wanda_neurons_fast.py:127-130, eval_coco.py:266-272).
@@ -90,6 +91,105 @@ def pndm_schedule(num_inference_steps=50, num_train_timesteps=1000, beta_start=0
     return plan
 
 
+@dataclass
+class SigmaSchedule:
+    """A sigma-parameterised schedule for sdmoe_cfg_x0_step: `timesteps` as the U-Net is given them, `sigmas` fp32
+    [steps + 1] ending in 0, the first input's two scales for sdmoe_prepare_input_scaled, and per step
+    plan[i] = (t, coef[6] = [cx, cm, a, b0, b1, in_scale], flags[2] = [use_prev, store_prev])."""
+    timesteps: np.ndarray
+    sigmas: np.ndarray
+    init_noise_sigma: float
+    first_in_scale: float
+    plan: list
+
+
+PREDICTION_TYPES = ("epsilon", "v_prediction")
+
+
+def _sigmas_at(timesteps, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012):
+    """Both sigma schedulers: the fp32 table ((1 - ac) / ac) ** 0.5 of the scaled_linear betas, interpolated at
+    `timesteps`, 0.0 appended (final_sigmas_type "zero"), fp32."""
+    betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+    ac = torch.cumprod(1.0 - betas, dim=0)
+    table = (((1 - ac) / ac) ** 0.5).numpy()
+    s = np.interp(np.asarray(timesteps, dtype=np.float64), np.arange(num_train_timesteps), table)
+    return np.concatenate([s, [0.0]]).astype(np.float32)
+
+
+def _check_prediction_type(prediction_type):
+    if prediction_type not in PREDICTION_TYPES:
+        raise ValueError(f"prediction_type must be 'epsilon' or 'v_prediction', got {prediction_type!r}")
+
+
+def euler_schedule(num_inference_steps=50, timestep_spacing="leading", prediction_type="epsilon", steps_offset=1,
+                   num_train_timesteps=1000):
+    """EulerDiscreteScheduler (s_churn = 0, no Karras sigmas) as stabilityai/stable-diffusion-xl-base-1.0 ("leading",
+    steps_offset 1, epsilon) and stabilityai/stable-diffusion-2 ("linspace", v_prediction) configure it, restated from
+    diffusers' scheduling_euler_discrete.py: pred_original_sample, derivative = (x - x0) / sigma and
+    x + derivative * (sigma' - sigma) collapse to x' = (sigma' / sigma) x + (1 - sigma' / sigma) x0. The "linspace"
+    timesteps are non-integer floats and reach the U-Net as they are. Coefficients are Python floats (float64) of the
+    fp32 sigma table; the C ABI rounds them to fp32 once."""
+    _check_prediction_type(prediction_type)
+    n = num_inference_steps
+    if timestep_spacing == "linspace":
+        ts = np.linspace(0, num_train_timesteps - 1, n, dtype=np.float32)[::-1].copy()
+    elif timestep_spacing == "leading":
+        ts = (np.arange(0, n) * (num_train_timesteps // n)).round()[::-1].astype(np.float32) + steps_offset
+    else:
+        raise ValueError(f"timestep_spacing must be 'leading' or 'linspace', got {timestep_spacing!r}")
+    sigmas = _sigmas_at(ts, num_train_timesteps)
+    smax = float(sigmas.max())
+    init = smax if timestep_spacing == "linspace" else (smax ** 2 + 1) ** 0.5
+    plan = []
+    for i in range(n):
+        s, sn = float(sigmas[i]), float(sigmas[i + 1])
+        if prediction_type == "epsilon":
+            cx, cm = 1.0, -s
+        else:
+            cx, cm = 1.0 / (s * s + 1), -s / (s * s + 1) ** 0.5
+        a = sn / s
+        plan.append((float(ts[i]), [cx, cm, a, 1.0 - a, 0.0, 1.0 / (sn * sn + 1) ** 0.5], [0, 0]))
+    return SigmaSchedule(ts, sigmas, init, 1.0 / (float(sigmas[0]) ** 2 + 1) ** 0.5, plan)
+
+
+def dpmpp_2m_schedule(num_inference_steps=50, prediction_type="epsilon", num_train_timesteps=1000):
+    """DPMSolverMultistepScheduler as stabilityai/stable-diffusion-2-1's config gives it (dpmsolver++, solver_order 2,
+    midpoint, lower_order_final, "linspace" spacing, final sigma 0, no Karras sigmas, no thresholding), restated from
+    diffusers' scheduling_dpmsolver_multistep.py. With alpha = 1 / sqrt(sigma^2 + 1), varsigma = sigma * alpha,
+    lambda = ln alpha - ln varsigma, h = lambda_t - lambda_s and E = -alpha_t * expm1(-h), the first-order update is
+    x' = (varsigma_t / varsigma_s) x + E x0 and the second-order one adds 0.5 E (x0 - prev_x0) / r0,
+    r0 = (lambda_s - lambda_{s-1}) / h. The first and the last step are first order; the last step has sigma' = 0
+    (lambda_t = +inf), where diffusers' arithmetic gives x0: (a, b0, b1) = (0, 1, 0), set directly and ahead of every
+    other case (a single step is the last step). No input scaling: init_noise_sigma and every in_scale are 1."""
+    import math
+    _check_prediction_type(prediction_type)
+    n = num_inference_steps
+    ts = np.linspace(0, num_train_timesteps - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+    sigmas = _sigmas_at(ts, num_train_timesteps)
+    alpha = [1.0 / (float(s) ** 2 + 1) ** 0.5 for s in sigmas]
+    vs = [float(s) * a for s, a in zip(sigmas, alpha)]
+    lam = [math.log(a) - math.log(v) for a, v in zip(alpha[:-1], vs[:-1])]  # lambda of sigma = 0 is never evaluated
+    plan = []
+    for i in range(n):
+        if prediction_type == "epsilon":
+            cx, cm = 1.0 / alpha[i], -vs[i] / alpha[i]
+        else:
+            cx, cm = alpha[i], -vs[i]
+        if i == n - 1:
+            a, b0, b1, use_prev = 0.0, 1.0, 0.0, 0
+        else:
+            h = lam[i + 1] - lam[i]
+            E = -alpha[i + 1] * math.expm1(-h)
+            a = vs[i + 1] / vs[i]
+            if i == 0:
+                b0, b1, use_prev = E, 0.0, 0
+            else:
+                r0 = (lam[i] - lam[i - 1]) / h
+                b0, b1, use_prev = E * (1 + 0.5 / r0), -0.5 * E / r0, 1
+        plan.append((int(ts[i]), [cx, cm, a, b0, b1, 1.0], [use_prev, int(i < n - 1)]))
+    return SigmaSchedule(ts, sigmas, 1.0, 1.0, plan)
+
+
 def prompt_embedding(prompt: str, dim: int = 768) -> torch.Tensor:
     """Seeded synthetic text conditioning [77, dim] fp32 (CPU) standing in for the CLIP text encoder."""
     rng = np.random.default_rng(zlib.crc32(prompt.encode("utf-8")))
@@ -133,15 +233,32 @@ class _HookHandle:
         self._fn = None
 
 
+SCHEDULERS = ("ddim", "pndm", "euler", "dpmpp_2m")
+
+
 class StableDiffusionPipeline:
     def __init__(self, unet: UNet2DConditionModel, device="cuda", num_inference_steps=50, guidance_scale=7.5,
                  scheduler="ddim", vae=None, text_encoder=None, tokenizer=None, text_encoder_2=None,
-                 tokenizer_2=None):
-        if scheduler not in ("ddim", "pndm"):
-            raise ValueError(f"scheduler must be 'ddim' or 'pndm', got {scheduler!r}")
+                 tokenizer_2=None, timestep_spacing=None, prediction_type="epsilon"):
+        if scheduler not in SCHEDULERS:
+            raise ValueError(f"scheduler must be one of {', '.join(map(repr, SCHEDULERS))}, got {scheduler!r}")
+        _check_prediction_type(prediction_type)
+        if prediction_type != "epsilon" and scheduler in ("ddim", "pndm"):
+            raise ValueError(f"scheduler {scheduler!r} is epsilon-only; prediction_type {prediction_type!r} needs "
+                             "'euler' or 'dpmpp_2m'")
         self.scheduler = scheduler  # "pndm": the reference's default (51 U-Net calls per 50 steps)
         self.unet = unet
         self.config = unet.config
+        self.prediction_type = prediction_type
+        # Euler only: "leading" on an SDXL config, "linspace" otherwise, as the checkpoints' scheduler configs
+        if scheduler == "euler":
+            timestep_spacing = timestep_spacing or ("leading" if self.is_sdxl else "linspace")
+            if timestep_spacing not in ("leading", "linspace"):
+                raise ValueError(f"timestep_spacing must be 'leading' or 'linspace', got {timestep_spacing!r}")
+        elif timestep_spacing is not None and (scheduler, timestep_spacing) not in (
+                ("ddim", "leading"), ("pndm", "leading"), ("dpmpp_2m", "linspace")):
+            raise ValueError(f"scheduler {scheduler!r} does not support timestep_spacing {timestep_spacing!r}")
+        self.timestep_spacing = timestep_spacing
         self.device = torch.device(device)
         self.num_inference_steps = num_inference_steps
         self.guidance_scale = guidance_scale
@@ -162,7 +279,7 @@ class StableDiffusionPipeline:
         RemoveNeuronsNoiseHPO (the loop calls unet.forward_nhwc, so a module forward hook never fires). eps is the
         loop's live fp16 [nimg * HW, OUT_PAD] buffer: channels 0..3 are the prediction, rows are [uncond x B ; cond x
         B] images of HW positions, and the next step overwrites it -- valid during the call only (copy what you keep:
-        ops.noise_capture). step_index counts U-Net calls (0..49 for DDIM, 0..50 for PNDM at 50 steps). The return
+        ops.noise_capture). step_index counts U-Net calls (0..49 for DDIM, Euler and DPM++ 2M, 0..50 for PNDM at 50 steps). The return
         value is ignored. Returns a handle whose .remove() unregisters fn."""
         self._unet_output_hooks.append(fn)
         return _HookHandle(self._unet_output_hooks, fn)
@@ -263,11 +380,23 @@ class StableDiffusionPipeline:
         HW = cfg.sample_size * cfg.sample_size
         x_in = torch.zeros((ncopy * B * HW, IN_PAD), dtype=torch.float16, device=self.device)
         eps = torch.empty((ncopy * B * HW, OUT_PAD), dtype=torch.float16, device=self.device)
-        ops.prepare_input(lat, x_in, ncopy)
         bufs = dict(lat=lat, x_in=x_in, eps=eps, ctx=ctx, add_hidden=add_hidden)
+        if self.scheduler in ("euler", "dpmpp_2m"):
+            sched = bufs["sigma_schedule"] = self.sigma_schedule(steps)
+            ops.prepare_input_scaled(lat, x_in, ncopy, sched.init_noise_sigma, sched.first_in_scale)
+        else:
+            ops.prepare_input(lat, x_in, ncopy)
         self._denoise(bufs, steps, g, do_cfg)
         out = PipelineOutput(images=self._finish(lat, output_type or self.output_type))
         return out
+
+    def sigma_schedule(self, steps):
+        """The SigmaSchedule of scheduler "euler" / "dpmpp_2m" for `steps` steps."""
+        if self.scheduler == "euler":
+            return euler_schedule(steps, self.timestep_spacing, self.prediction_type)
+        if self.scheduler == "dpmpp_2m":
+            return dpmpp_2m_schedule(steps, self.prediction_type)
+        raise ValueError(f"scheduler {self.scheduler!r} has no sigma schedule")
 
     def _denoise(self, bufs, steps, g, do_cfg):
         """The denoising loop over bufs (lat, x_in, eps, ctx, add_hidden)."""
@@ -292,6 +421,24 @@ class StableDiffusionPipeline:
                     if hooks:
                         self._after_unet(i, eps, HW)
                     ops.cfg_multistep_step(eps, lat, do_cfg, g, hist, cur, coef, flags, next_in=x_in)
+                body()
+        elif self.scheduler in ("euler", "dpmpp_2m"):
+            # x_in already holds the scaled first input (__call__: prepare_input_scaled with this schedule's scales)
+            plan = (bufs.get("sigma_schedule") or self.sigma_schedule(steps)).plan
+            prev_x0 = None
+            if any(f[0] or f[1] for _, _, f in plan):  # DPM++ only; allocated on first use
+                if "prev_x0" not in bufs:
+                    bufs["prev_x0"] = torch.zeros_like(lat)
+                prev_x0 = bufs["prev_x0"]
+            if "table" not in bufs:
+                bufs["table"] = time_table([t for t, _, _ in plan])  # loop-invariant: all steps at once
+            table = bufs["table"]
+            for i, (t, coef, flags) in enumerate(plan):
+                def body(i=i, t=t, coef=coef, flags=flags):
+                    self.unet.forward_nhwc(x_in, float(t), ctx, out=eps, add_hidden=add_hidden, temb=temb_row(table, i))
+                    if hooks:
+                        self._after_unet(i, eps, HW)
+                    ops.cfg_x0_step(eps, lat, do_cfg, g, prev_x0, coef, flags, next_in=x_in)
                 body()
         else:
             ts, a_t, a_prev = ddim_schedule(steps)

@@ -523,6 +523,34 @@ int sdmoe_cfg_multistep_step(const void* eps, long lde, float* lat, int B, int H
                              void* stream);
 
 /*
+ * Classifier-free guidance + one step of a sigma-parameterised scheduler on fp32 NCHW latents in place: diffusers'
+ * EulerDiscreteScheduler and DPMSolverMultistepScheduler (dpmsolver++, order 2, midpoint), each with prediction_type
+ * "epsilon" or "v_prediction" (the reference's SDXL, SD-2 and SD-2.1 configurations, utils.py:91-112), reduced to one
+ * per-element form. Layouts as sdmoe_cfg_ddim_step: lat and prev_x0 fp32 [B,4,HW]; eps fp16 rows [ncopy*B*HW, lde],
+ * uncond images first, channels 0..3; next_in (may be NULL) fp16 rows [ncopy*B*HW, ldn], channels 0..3 written only.
+ * Host-computed per step (pipeline.euler_schedule / pipeline.dpmpp_2m_schedule):
+ *   coef[6] = {cx, cm, a, b0, b1, in_scale}, flags[2] = {use_prev, store_prev}
+ * The order within an element is fixed:
+ *   1. m = CFG(eps); read x = lat; read p = prev_x0 if use_prev
+ *   2. x0 = cx*x + cm*m;  x' = a*x + b0*x0 (+ b1*p if use_prev)
+ *   3. prev_x0 = x0 if store_prev
+ *   4. lat = x';  next_in = fp16(x' * in_scale) for both CFG copies
+ * With use_prev == 0 the prev_x0 buffer is never read (it may hold anything, NaN included). prev_x0 may be NULL only
+ * when both flags are 0 (SDMOE_EARG otherwise). lde and ldn must be multiples of 4.
+ */
+int sdmoe_cfg_x0_step(const void* eps, long lde, float* lat, int B, int HW, int do_cfg, float guidance,
+                      float* prev_x0, const float* coef, const int* flags, void* next_in, long ldn, void* stream);
+
+/*
+ * sdmoe_prepare_input for a scheduler with an init_noise_sigma and a scale_model_input: lat = lat * lat_scale in
+ * place (diffusers' latents * scheduler.init_noise_sigma), then out = fp16(lat * in_scale) for ncopy copies (the
+ * first step's scale_model_input). Two separately rounded fp32 products. With both scales 1 the output is
+ * bit-identical to sdmoe_prepare_input's and lat is unchanged.
+ */
+int sdmoe_prepare_input_scaled(float* lat, void* out, int B, int HW, long ldo, int ncopy, float lat_scale,
+                               float in_scale, void* stream);
+
+/*
  * The noise-HPO objective (the reference's modularity/remove_experts_noise_hpo.py:74-84) on device stores of the
  * U-Net's per-step output.
  * sdmoe_noise_capture: channels 0..3 of each of `rows` fp16 rows of eps (leading dimension lde, e.g. the pipeline's
