@@ -70,6 +70,11 @@ SIGNATURES = {
     "sdmoe_clip_resample_h": [_P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P],
     "sdmoe_clip_resample_v": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _FP, _FP, _P, _P, _L, _I, _P],
     "sdmoe_clip_scores": [_P, _L, _P, _L, _P, _L, _I, _I, _P, _P],
+    "sdmoe_stem_rows": [_P, _I, _I, _FP, _FP, _P, _L, _I, _P],
+    "sdmoe_maxpool3x3s2": [_P, _L, _I, _I, _I, _I, _P, _L, _P],
+    "sdmoe_avgpool_rows": [_P, _L, _I, _I, _I, _P, _L, _P],
+    "sdmoe_add_relu": [_P, _P, _P, _L, _P],
+    "sdmoe_topk_hits": [_P, _L, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P],
     "sdmoe_text_pool": [_P, _L, _I, _I, _I, _I, _I, _P, _L, _P],
     "sdmoe_concept_route": [_P, _L, _I, _I, _I, _P, _L, _I, _P, _P, _I, _P, _P, _P, _P],
     "sdmoe_softmax_rows": [_P, _L, _P, _L, _I, _I, _P],

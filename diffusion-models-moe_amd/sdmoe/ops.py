@@ -1193,14 +1193,31 @@ def _bicubic(x):
     return 0.0
 
 
-def clip_resample_coeffs(in_size: int, out_size: int, first: int = 0, count: int | None = None):
-    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for outputs [first, first + count) of a bicubic resize of
-    one axis from in_size to out_size, in float64 scalar arithmetic in Pillow's operation order: (bounds, kk, ksize),
-    bounds = [(first tap, taps)], kk = rows of ksize 22-bit fixed-point integer weights (zero past the taps)."""
+def _triangle(x):
+    """Pillow's bilinear_filter."""
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return 1.0 - x
+    return 0.0
+
+
+RESAMPLE_FILTERS = {"bicubic": (_bicubic, 2.0), "bilinear": (_triangle, 1.0)}  # name -> (filter, support)
+
+
+def clip_resample_coeffs(in_size: int, out_size: int, first: int = 0, count: int | None = None,
+                         filter: str = "bicubic"):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for outputs [first, first + count) of a resize of one axis
+    from in_size to out_size with `filter` (RESAMPLE_FILTERS: Image.BICUBIC, the default, or Image.BILINEAR), in
+    float64 scalar arithmetic in Pillow's operation order: (bounds, kk, ksize), bounds = [(first tap, taps)], kk =
+    rows of ksize 22-bit fixed-point integer weights (zero past the taps)."""
+    if filter not in RESAMPLE_FILTERS:
+        raise ValueError(f"clip_resample_coeffs: filter {filter!r} is not one of {sorted(RESAMPLE_FILTERS)}")
+    fn, fsupport = RESAMPLE_FILTERS[filter]
     count = out_size - first if count is None else count
     scale = in_size / out_size
     fs = max(scale, 1.0)
-    support = 2.0 * fs
+    support = fsupport * fs
     ksize = int(-(-support // 1)) * 2 + 1
     ss = 1.0 / fs
     bounds, kk = [], []
@@ -1209,7 +1226,7 @@ def clip_resample_coeffs(in_size: int, out_size: int, first: int = 0, count: int
         xmin = max(int(center - support + 0.5), 0)
         xmax = min(int(center + support + 0.5), in_size)
         n = xmax - xmin
-        w = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(n)]
+        w = [fn((x + xmin - center + 0.5) * ss) for x in range(n)]
         ww = 0.0
         for v in w:
             ww += v
@@ -1228,16 +1245,29 @@ def clip_resize_shape(H: int, W: int, size: int):
     return (size, new_long) if H <= W else (new_long, size)
 
 
-class ClipResamplePlan:
-    """Device tables of the resize (shortest edge -> S) + centre crop S x S of H x W images: only the crop window's
-    columns and rows, and the input rows [row0, row0 + nrows) the vertical pass reads."""
+def centre_crop_offsets(oh: int, ow: int, size: int, half_even: bool = False):
+    """(top, left) of a size x size centre crop of an oh x ow image: transformers' (oh - size) // 2, or with half_even
+    torchvision's int(round((oh - size) / 2.0)) (Python's round: a difference ending in .5 goes to the even offset)."""
+    if half_even:
+        return int(round((oh - size) / 2.0)), int(round((ow - size) / 2.0))
+    return (oh - size) // 2, (ow - size) // 2
 
-    def __init__(self, H, W, S, device):
-        oh, ow = clip_resize_shape(H, W, S)
-        self.H, self.W, self.S = H, W, S
-        self.top, self.left = (oh - S) // 2, (ow - S) // 2
-        bx, kx, self.ksx = clip_resample_coeffs(W, ow, self.left, S)
-        by, ky, self.ksy = clip_resample_coeffs(H, oh, self.top, S)
+
+class ClipResamplePlan:
+    """Device tables of the resize (shortest edge -> `resize`, S by default) + centre crop S x S of H x W images: only
+    the crop window's columns and rows, and the input rows [row0, row0 + nrows) the vertical pass reads. filter and
+    half_even choose the preset: CLIPImageProcessor's (bicubic, floor crop offsets; the default) or torchvision's
+    ImageClassification (bilinear, resize 232 > crop 224, half-even crop offsets)."""
+
+    def __init__(self, H, W, S, device, *, resize=None, filter="bicubic", half_even=False):
+        resize = S if resize is None else int(resize)
+        if resize < S:
+            raise ValueError(f"resize {resize} is smaller than the crop {S}")
+        oh, ow = clip_resize_shape(H, W, resize)
+        self.H, self.W, self.S, self.resize = H, W, S, resize
+        self.top, self.left = centre_crop_offsets(oh, ow, S, half_even)
+        bx, kx, self.ksx = clip_resample_coeffs(W, ow, self.left, S, filter)
+        by, ky, self.ksy = clip_resample_coeffs(H, oh, self.top, S, filter)
         self.row0 = min(lo for lo, _ in by)
         self.nrows = max(lo + n for lo, n in by) - self.row0
         if min(lo for lo, _ in bx) < 0 or max(lo + n for lo, n in bx) > W or self.row0 < 0 \
@@ -1253,11 +1283,12 @@ class ClipResamplePlan:
 _CLIP_PLANS = {}
 
 
-def clip_resample_plan(H, W, S, device) -> ClipResamplePlan:
-    key = (int(H), int(W), int(S), str(device))
+def clip_resample_plan(H, W, S, device, *, resize=None, filter="bicubic", half_even=False) -> ClipResamplePlan:
+    key = (int(H), int(W), int(S), str(device), None if resize is None else int(resize), filter, bool(half_even))
     plan = _CLIP_PLANS.get(key)
     if plan is None:
-        plan = _CLIP_PLANS[key] = ClipResamplePlan(int(H), int(W), int(S), device)
+        plan = _CLIP_PLANS[key] = ClipResamplePlan(int(H), int(W), int(S), device, resize=resize, filter=filter,
+                                                   half_even=half_even)
     return plan
 
 
@@ -1267,11 +1298,13 @@ def clip_padded_k(patch: int) -> int:
 
 
 def clip_preprocess(u8, size: int, patch: int = 0, *, a_out=None, u8_out=None, mean=CLIP_IMAGE_MEAN,
-                    std=CLIP_IMAGE_STD):
+                    std=CLIP_IMAGE_STD, resize=None, filter="bicubic", half_even=False):
     """CLIPImageProcessor on the device for u8 [B, H, W, 3] uint8: Pillow-exact bicubic resize (shortest edge -> size),
     centre crop size x size (sdmoe_clip_resample_h / _v). a_out: fp16 [B * (size / patch)^2, >= clip_padded_k(patch)]
     row view that receives the normalised, patchified pixels (the patch GEMM's A operand, padding columns zero);
-    u8_out: uint8 [B, size, size, 3] that receives the cropped pixels. Returns (a_out, u8_out)."""
+    u8_out: uint8 [B, size, size, 3] that receives the cropped pixels. Returns (a_out, u8_out).
+    resize / filter / half_even (ClipResamplePlan) select another preset on the same kernels: torchvision's
+    ImageClassification is resize=232, size=224, filter="bilinear", half_even=True."""
     lib = _lib.load()
     if u8.dim() != 4 or u8.shape[3] != 3:
         raise ValueError(f"clip_preprocess: expected [B, H, W, 3] uint8, got {tuple(u8.shape)}")
@@ -1280,7 +1313,7 @@ def clip_preprocess(u8, size: int, patch: int = 0, *, a_out=None, u8_out=None, m
     up = _dev(u8, "u8", torch.uint8)
     B, H, W, _ = u8.shape
     S = int(size)
-    plan = clip_resample_plan(H, W, S, u8.device)
+    plan = clip_resample_plan(H, W, S, u8.device, resize=resize, filter=filter, half_even=half_even)
     ap, lda, kpad = None, 0, 0
     if a_out is not None:
         if patch <= 0 or S % patch:
@@ -1322,6 +1355,101 @@ def clip_scores(T, A, R, out=None):
     st = lib.sdmoe_clip_scores(tp, ldt, ap, lda, rp, ldr, n, D, _dev(out, "out", torch.float64), _stream())
     _lib.check(st, "sdmoe_clip_scores")
     return out
+
+
+IMAGENET_MEAN = (0.485, 0.456, 0.406)   # torchvision ImageClassification preset
+IMAGENET_STD = (0.229, 0.224, 0.225)
+STEM_K, STEM_KPAD = 147, 192  # 3 x 7 x 7 taps, padded to the GEMM's K granule (64)
+
+
+def stem_rows(u8, out=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """u8 [B, S, S, 3] uint8 -> fp16 [B * So^2, STEM_KPAD], So = (S - 1) // 2 + 1: the normalised im2col rows of the
+    7x7 / stride 2 / padding 3 stem (sdmoe_stem_rows); the stem is then linear(rows, w[64, STEM_KPAD], act=ACT_RELU)."""
+    lib = _lib.load()
+    if u8.dim() != 4 or u8.shape[3] != 3 or u8.shape[1] != u8.shape[2]:
+        raise ValueError(f"stem_rows: expected [B, S, S, 3] uint8, got {tuple(u8.shape)}")
+    B, S = u8.shape[0], u8.shape[1]
+    So = (S - 1) // 2 + 1
+    if out is None:
+        out = torch.empty((B * So * So, STEM_KPAD), dtype=torch.float16, device=u8.device)
+    op, lda = _rows(out, "out")
+    if out.shape[0] != B * So * So or out.shape[1] < STEM_K:
+        raise ValueError(f"stem_rows: out {tuple(out.shape)} is not [{B * So * So}, >= {STEM_K}]")
+    f3 = ctypes.c_float * 3
+    st = lib.sdmoe_stem_rows(_dev(u8, "u8", torch.uint8), B, S, f3(*mean), f3(*std), op, lda, out.shape[1], _stream())
+    _lib.check(st, "sdmoe_stem_rows")
+    return out
+
+
+def maxpool3x3s2(x, nimg, H, W, out=None):
+    """F.max_pool2d(x, 3, 2, 1) on NHWC x viewed as [nimg*H*W, C] -> [nimg*OH*OW, C] (sdmoe_maxpool3x3s2)."""
+    lib = _lib.load()
+    xp, ldx = _rows(x, "x")
+    C = x.shape[1]
+    if x.shape[0] != nimg * H * W:
+        raise ValueError("maxpool3x3s2: rows != nimg*H*W")
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if out is None:
+        out = torch.empty((nimg * OH * OW, C), dtype=torch.float16, device=x.device)
+    op, ldy = _rows(out, "out")
+    if tuple(out.shape) != (nimg * OH * OW, C):
+        raise ValueError(f"maxpool3x3s2: out {tuple(out.shape)} is not {(nimg * OH * OW, C)}")
+    _lib.check(lib.sdmoe_maxpool3x3s2(xp, ldx, nimg, H, W, C, op, ldy, _stream()), "sdmoe_maxpool3x3s2")
+    return out
+
+
+def avgpool_rows(x, nimg, HW, out=None):
+    """[nimg*HW, C] -> [nimg, C]: per image and channel fp16(fp32 sum in row order / HW) (sdmoe_avgpool_rows)."""
+    lib = _lib.load()
+    xp, ldx = _rows(x, "x")
+    C = x.shape[1]
+    if x.shape[0] != nimg * HW:
+        raise ValueError("avgpool_rows: rows != nimg*HW")
+    if out is None:
+        out = torch.empty((nimg, C), dtype=torch.float16, device=x.device)
+    op, ldy = _rows(out, "out")
+    if tuple(out.shape) != (nimg, C):
+        raise ValueError(f"avgpool_rows: out {tuple(out.shape)} is not {(nimg, C)}")
+    _lib.check(lib.sdmoe_avgpool_rows(xp, ldx, nimg, HW, C, op, ldy, _stream()), "sdmoe_avgpool_rows")
+    return out
+
+
+def add_relu(a, b, out=None):
+    """out = relu(a + b) on contiguous fp16 tensors of one shape, any element count; out may be a or b
+    (sdmoe_add_relu)."""
+    lib = _lib.load()
+    if a.shape != b.shape:
+        raise ValueError(f"add_relu: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+    if out is None:
+        out = torch.empty_like(a)
+    elif out.shape != a.shape:
+        raise ValueError(f"add_relu: out {tuple(out.shape)} is not {tuple(a.shape)}")
+    st = lib.sdmoe_add_relu(_dev(a, "a"), _dev(b, "b"), _dev(out, "out"), a.numel(), _stream())
+    _lib.check(st, "sdmoe_add_relu")
+    return out
+
+
+def topk_hits(logits, table, label, k=5):
+    """Top-k classes of fp16 logits [n, C] and their match against a label bit table (sdmoe_topk_hits): table uint32
+    words [G, ceil(C / 32)] held as an int32 device tensor, label int32 [n]. Returns device int32 tensors (topk [n, k]
+    descending, ties to the lower id, NaN first; hit [n]; total [1]); a label outside [0, G) gives hit -1 and total -1."""
+    lib = _lib.load()
+    lp, ldl = _rows(logits, "logits")
+    n, C = logits.shape
+    if not 1 <= k <= min(C, 8):
+        raise ValueError(f"topk_hits: k={k} is not in [1, min(C={C}, 8)]")
+    if table.dim() != 2 or table.shape[1] != (C + 31) // 32:
+        raise ValueError(f"topk_hits: table {tuple(table.shape)} is not [G, {(C + 31) // 32}]")
+    if label.numel() != n:
+        raise ValueError(f"topk_hits: {label.numel()} labels for {n} rows")
+    topk = torch.empty((n, k), dtype=torch.int32, device=logits.device)
+    hit = torch.empty(n, dtype=torch.int32, device=logits.device)
+    total = torch.empty(1, dtype=torch.int32, device=logits.device)
+    st = lib.sdmoe_topk_hits(lp, ldl, n, C, k, _dev(table, "table", torch.int32), table.shape[0],
+                             _dev(label, "label", torch.int32), topk.data_ptr(), hit.data_ptr(), total.data_ptr(),
+                             _stream())
+    _lib.check(st, "sdmoe_topk_hits")
+    return topk, hit, total
 
 
 POOL_MAX_D = 2048  # sdmoe_text_pool / sdmoe_concept_route: 256 chunks of 8 columns

@@ -17,10 +17,33 @@ accumulation like the text encoder. There is no host path: images not on a GPU r
 """
 from __future__ import annotations
 
+import json
+
 import torch
 
 from . import ops
 from .clip import CLIPModel
+from .resnet import ResNet
+
+
+def _u8_batches(images):
+    """images -> list of contiguous uint8 [b, H, W, 3] device batches (quantised where they are floats)."""
+    items = list(images) if isinstance(images, (list, tuple)) else [images]
+    out = []
+    for t in items:
+        if not torch.is_tensor(t):
+            raise TypeError(f"images must be device tensors, got {type(t).__name__}")
+        if t.dim() == 3:
+            t = t[None]
+        if t.dim() != 4:
+            raise ValueError(f"image tensor of shape {tuple(t.shape)}: expected [B, 3, H, W] or [B, H, W, 3]")
+        if t.dtype == torch.uint8:
+            if t.shape[3] != 3:
+                raise ValueError(f"uint8 images must be NHWC [B, H, W, 3], got {tuple(t.shape)}")
+            out.append(t.contiguous())
+        else:
+            out.append(ops.clip_quantise(t.contiguous()))
+    return out
 
 
 class ClipScorer:
@@ -44,23 +67,7 @@ class ClipScorer:
 
     # -- front end ---------------------------------------------------------------------------------------------
     def _u8_batches(self, images):
-        """images -> list of contiguous uint8 [b, H, W, 3] device batches (quantised where they are floats)."""
-        items = list(images) if isinstance(images, (list, tuple)) else [images]
-        out = []
-        for t in items:
-            if not torch.is_tensor(t):
-                raise TypeError(f"images must be device tensors, got {type(t).__name__}")
-            if t.dim() == 3:
-                t = t[None]
-            if t.dim() != 4:
-                raise ValueError(f"image tensor of shape {tuple(t.shape)}: expected [B, 3, H, W] or [B, H, W, 3]")
-            if t.dtype == torch.uint8:
-                if t.shape[3] != 3:
-                    raise ValueError(f"uint8 images must be NHWC [B, H, W, 3], got {tuple(t.shape)}")
-                out.append(t.contiguous())
-            else:
-                out.append(ops.clip_quantise(t.contiguous()))
-        return out
+        return _u8_batches(images)
 
     def _run(self, images, want_a, want_u8):
         batches = self._u8_batches(images)
@@ -138,3 +145,111 @@ class ClipScorer:
         with open(path, "w") as f:
             f.write(f"Average CLIP score: {result['average_clipscore']}\n")
             f.write(f"Average accuracy: {result['average_acc']}\n")
+
+
+def match_table(categories, labels):
+    """The reference's top-k name match (benchmarks/object_erase.py:253-284) as a bit table: int32 [len(labels),
+    ceil(len(categories) / 32)] holding uint32 words, bit c % 32 of word c // 32 of row g set where class c counts as
+    a hit for label g. The label is stripped and split on spaces; a class is a hit if any space-separated word of its
+    category name is among the label's words. Names are compared as given: the reference lower-cases its labels but
+    not the category names, so a capitalised name word never matches ("English springer" matches through "springer",
+    never through "English"). That quirk is kept."""
+    words = (len(categories) + 31) // 32
+    rows = []
+    for label in labels:
+        want = set(label.strip().split(" "))
+        row = [0] * words
+        for c, name in enumerate(categories):
+            if any(w in want for w in name.split(" ")):
+                row[c >> 5] |= 1 << (c & 31)
+        rows.append(row)
+    t = torch.tensor(rows, dtype=torch.int64).reshape(len(rows), words)
+    return torch.where(t >= 1 << 31, t - (1 << 32), t).to(torch.int32)
+
+
+class ObjectScorer:
+    """Object-erasure accuracy (the reference's Imagenette experiment, benchmarks/object_erase.py:247-302 and
+    save_union_over_time.py:264-276): every removal image through torchvision's ImageClassification preset and
+    resnet50, the top-5 class names matched word by word against the prompt's label, acc = hits / n.
+
+    The reference scores one reloaded PNG per call on the host. Here the images stay on the device:
+
+        quantise (diffusers numpy_to_pil)    sdmoe_clip_quantise
+        Pillow-exact bilinear resize to      sdmoe_clip_resample_h/v with the triangle filter's tables, crop offsets
+          `resize`, centre crop `size`         int(round((h - size) / 2.0)) (half-even, torchvision's center_crop)
+        to_tensor, normalize, stem im2col    sdmoe_stem_rows
+        ResNet                               sdmoe.resnet.ResNet, a whole batch in one pass
+        top-k, name match, hit count         sdmoe_topk_hits: n k + n + 1 integers leave the device
+
+    model: sdmoe.resnet.ResNet; categories: the class names in class-id order (the caller's data, e.g.
+    ResNet50_Weights.DEFAULT.meta["categories"]) or None -- then only the methods that need no names work.
+    `images` as for ClipScorer: [B, 3, H, W] floats in [0, 1], [B, H, W, 3] uint8, or a list of such (sizes may
+    differ), all on the device. torchvision's tensor-input antialias path is not reproduced: the preset is applied
+    as on a PIL image, which is what the reference feeds it."""
+
+    def __init__(self, model: ResNet, categories=None, size: int = 224, resize: int = 232):
+        model.config.check_size(size)
+        if resize < size:
+            raise ValueError(f"resize {resize} is smaller than the crop {size}")
+        if categories is not None and len(categories) != model.config.num_classes:
+            raise ValueError(f"{len(categories)} category names for {model.config.num_classes} classes")
+        self.model = model
+        self.categories = None if categories is None else list(categories)
+        self.size, self.resize = int(size), int(resize)
+        self._tables = {}
+
+    def preprocess_u8(self, images):
+        """The resized, centre-cropped uint8 pixels [n, size, size, 3] (what the preset's to_tensor sees)."""
+        batches = _u8_batches(images)
+        n, S = sum(b.shape[0] for b in batches), self.size
+        u8 = torch.empty((n, S, S, 3), dtype=torch.uint8, device=batches[0].device)
+        b0 = 0
+        for b in batches:
+            ops.clip_preprocess(b, S, u8_out=u8[b0:b0 + b.shape[0]], resize=self.resize, filter="bilinear",
+                                half_even=True)
+            b0 += b.shape[0]
+        return u8
+
+    def logits(self, images):
+        """fp16 [n, num_classes], all images in one pass."""
+        return self.model(self.preprocess_u8(images))
+
+    def _table(self, labels):
+        """(device bit table over the distinct labels, device int32 label row per image)."""
+        if self.categories is None:
+            raise ValueError("ObjectScorer was built without category names (categories=None)")
+        distinct = sorted(set(labels))
+        key = tuple(distinct)
+        table = self._tables.get(key)
+        if table is None:
+            table = self._tables[key] = match_table(self.categories, distinct).to(self.model.device)
+        row = {lab: g for g, lab in enumerate(distinct)}
+        return table, torch.tensor([row[lab] for lab in labels], dtype=torch.int32).to(self.model.device)
+
+    def topk(self, images, k: int = 5):
+        """The k best class ids per image, int32 [n, k] on the host, descending (ties to the lower id)."""
+        lg = self.logits(images)
+        n = lg.shape[0]
+        table = torch.zeros((1, (lg.shape[1] + 31) // 32), dtype=torch.int32, device=lg.device)
+        return ops.topk_hits(lg, table, torch.zeros(n, dtype=torch.int32, device=lg.device), k)[0].cpu()
+
+    def score_erasure(self, images, labels, k: int = 5):
+        """object_erase.py:253-302 for n images and their n labels (lower-cased object names, as the reference's
+        prompts CSV carries them): {"acc": hits / n, "hits": int32 [n], "topk": int32 [n, k]} (host tensors)."""
+        labels = [labels] if isinstance(labels, str) else list(labels)
+        table, rows = self._table(labels)
+        lg = self.logits(images)
+        if lg.shape[0] != len(labels):
+            raise ValueError(f"{len(labels)} labels but {lg.shape[0]} images")
+        topk, hit, total = ops.topk_hits(lg, table, rows, k)
+        out = torch.cat([topk.reshape(-1), hit, total]).cpu()
+        n = len(labels)
+        if out[-1].item() < 0:
+            raise ops._lib.SdmoeError("sdmoe_topk_hits: a label row outside the match table")
+        return {"acc": out[-1].item() / n, "hits": out[n * k:n * k + n], "topk": out[:n * k].reshape(n, k)}
+
+    @staticmethod
+    def write_results(path, result):
+        """results.json in the reference's format (object_erase.py:300-302)."""
+        with open(path, "w") as f:
+            json.dump({"acc": result["acc"]}, f)

@@ -608,6 +608,41 @@ int sdmoe_clip_scores(const void* T, long ldt, const void* A, long lda, const vo
                       double* out, void* stream);
 
 /*
+ * The object-erasure scorer's CNN pieces and score reduction (csrc/imagenet.hip): what torchvision's resnet50 needs
+ * beyond sdmoe_linear / sdmoe_conv3x3, and the top-k label match. Replaces: the per-image host classifier pass and
+ * the Python name matching of benchmarks/object_erase.py:247-302 and benchmarks/save_union_over_time.py:264-276.
+ * Streaming kernels, 16-byte accesses where pointers and strides allow (16-byte aligned, strides % 8 == 0) and an
+ * element-wise path otherwise; no atomics, fixed summation order: bit-identical from run to run.
+ * sdmoe_stem_rows: u8 uint8 [B, S, S, 3] (contiguous) -> A fp16 [B So^2, kpad] (row stride lda), So = (S - 1) / 2 + 1:
+ *   the im2col rows of a 7x7 / stride 2 / padding 3 conv. Row b So^2 + oy So + ox, column c 49 + ky 7 + kx (the
+ *   flattening of torch's [Cout, 3, 7, 7] weight) = fp16(((u8 * (1/255)) - mean[c]) / std[c]) of input pixel
+ *   (2 oy - 3 + ky, 2 ox - 3 + kx), each step rounded in fp32; 0 where the tap lies outside the image (the padding is
+ *   applied after the normalisation) and in columns [147, kpad). kpad >= 147, lda >= kpad. mean, std: 3 host floats.
+ *   Replaces torchvision's to_tensor / normalize and the unfold of ResNet.conv1; the stem is then one sdmoe_linear.
+ * sdmoe_maxpool3x3s2: X fp16 NHWC [B, H, W, C] (pixel stride ldx) -> Y [B, OH, OW, C] (pixel stride ldy), OH =
+ *   (H - 1) / 2 + 1, OW likewise: max over the 3x3 window at stride 2, padding 1. Padding never wins (-inf), NaN
+ *   propagates, the first of equal values is kept: torch.nn.functional.max_pool2d(x, 3, 2, 1) bit for bit. C % 8 == 0.
+ * sdmoe_avgpool_rows: X fp16 [B * HW, C] (row stride ldx) -> Y fp16 [B, C] (row stride ldy): fp16(s / HW) with s the
+ *   fp32 sum of the image's HW rows in row order. C % 8 == 0. Replaces AdaptiveAvgPool2d(1) + flatten.
+ * sdmoe_add_relu: out[i] = relu(fp16(float(a[i]) + float(b[i]))), i < n, any n and any 2-byte alignment; negative
+ *   sums give +0, -0 and NaN pass through (torch.relu(a + b)). out may alias a or b.
+ * sdmoe_topk_hits: logits fp16 [n, C] (row stride ldl), 1 <= k <= min(C, 8) -> topk int32 [n, k]: per row the k best
+ *   class ids in descending logit order, ties (-0 == +0) to the lower id, NaN above +inf (torch.topk's ranking, so a
+ *   broken run shows). table uint32 [G, ceil(C / 32)]: bit c % 32 of word c / 32 of row g is set where class c counts
+ *   as a hit for label g; label int32 [n]. hit int32 [n] = 1 if one of the row's k classes is set in row label[i],
+ *   else 0; total int32 [1] = sum of hit, taken in image order by one block. label is range-checked on the device:
+ *   a label outside [0, G) reads no table row and gives hit[i] = -1 and total = -1 (the error status; the entry
+ *   point itself cannot see device data). One wave per image.
+ */
+int sdmoe_stem_rows(const void* u8, int B, int S, const float* mean, const float* std, void* A, long lda, int kpad,
+                    void* stream);
+int sdmoe_maxpool3x3s2(const void* X, long ldx, int B, int H, int W, int C, void* Y, long ldy, void* stream);
+int sdmoe_avgpool_rows(const void* X, long ldx, int B, int HW, int C, void* Y, long ldy, void* stream);
+int sdmoe_add_relu(const void* a, const void* b, void* out, long n, void* stream);
+int sdmoe_topk_hits(const void* logits, long ldl, int n, int C, int k, const unsigned* table, int G, const int* label,
+                    int* topk, int* hit, int* total, void* stream);
+
+/*
  * The concept checkers' decision step on the device (csrc/concepts.hip): from fp16 text-encoder hidden-state rows to
  * the per-prompt select words of sdmoe_wmask_union_sets, with no host round trip. float64 arithmetic in one fixed
  * order, no atomics: bit-identical from run to run.
